@@ -1,6 +1,6 @@
 """Headline benchmark: env-steps/s of the batched MI355X physics step.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -21,19 +21,28 @@ fp32.
 N>1 (one process per GPU, `dm_control_amd.distributed`): envs are independent,
 so the env axis is sharded contiguously and NO collective runs in the step.
   default          weak scaling: --batch envs per GPU (8192); `value` is this.
-                   For N > 1 the same line also carries `strong`: BASELINE
-                   configs[3], humanoid-walk with 8192 envs in total sharded
-                   shard_range(8192, N, rank) per GPU (1024 per GPU at N = 8)
+                   For N > 1 with --full the same line also carries `strong`:
+                   BASELINE configs[3], humanoid-walk with 8192 envs in total
+                   sharded shard_range(8192, N, rank) per GPU (1024 per GPU at
+                   N = 8)
   --global-batch G strong scaling only: G envs in total of --domain/--task
 The only collective is the RCCL all-gather of per-env episode returns on the
 reporting path, after the timed region.
 
 Rank 0 prints ONE JSON line with `roofline` (HIP events on the batch's own
-stream) and, at N=1, `cpu_baseline` (the fp64 CPU oracle = "port"; libmujoco
-itself is a closed binary that is not available here) including the second
-half of BASELINE's metric, qpos rel-err vs the CPU step (teacher-forced per
-step, and free-running at 100 / 1000 steps with the step of the first
-contact-count mismatch).
+stream).  A plain run does only that: set-up, warm-up, the timed steps, the
+line.  `--full` adds the legs that take runs of their own: at N=1
+`cpu_baseline` (the fp64 CPU oracle = "port"; libmujoco itself is a closed
+binary that is not available here) including the second half of BASELINE's
+metric, qpos rel-err vs the CPU step (teacher-forced per step, and
+free-running at 100 / 1000 steps with the step of the first contact-count
+mismatch), and `tolerance_compliant` (a short fp64 leg); at N>1 `strong`.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+the step receives it, to DIR/<name>.npy (`qpos`, `qvel`, and `observation`,
+`reward` where the kernel computes the task; [env][k], the batch's precision;
+a fixed sample of envs when the whole batch exceeds DUMP_BYTES).  The actions
+and initial states are seeded, so two builds can be compared output for output.
 """
 
 import argparse
@@ -54,6 +63,7 @@ SIMDS = 1024            # 256 CUs x 4
 VALU_CYCLES = 2         # wave64 fp32 VALU instruction on a SIMD-32: peak issue rate
 VALU_CYCLES_ONE_WAVE = 4  # what a wave that has the SIMD to itself sustains
 CLOCK_GHZ = 2.4
+DUMP_BYTES = 60*10**6   # --dump-outputs: at most this much array data in all
 
 
 def algorithmic_bytes_per_env_step(info, real_size):
@@ -296,6 +306,33 @@ def _free_run_sample(gpu_batch, om, oracle, nsub, cores, nenv=64, steps=1000):
   return out
 
 
+def dump_outputs(batch, directory, prefix=''):
+  """Writes the step's outputs of every env (or of a seeded sample of envs,
+  the same for the same batch size) as float32 / float64 .npy files."""
+  from dm_control_amd import wrapper as W
+  info = batch.model.info
+  fields = [('qpos', W.FIELD_QPOS), ('qvel', W.FIELD_QVEL)]
+  if info.nobs > 0:
+    fields += [('observation', W.FIELD_OBS), ('reward', W.FIELD_REWARD)]
+  arrays = {}
+  for name, field in fields:
+    a = batch.read(field)
+    arrays[name] = a if field in (W.FIELD_OBS, W.FIELD_REWARD) else a.T
+  nenv = batch.nenv
+  per_env = sum(a.nbytes for a in arrays.values())//nenv
+  keep = None
+  if per_env*nenv > DUMP_BYTES:
+    keep = np.sort(np.random.RandomState(0).choice(
+        nenv, DUMP_BYTES//per_env, replace=False))
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    if keep is not None:
+      a = a[keep]
+    np.save(os.path.join(directory, prefix + name + '.npy'), np.ascontiguousarray(a))
+  sys.stderr.write('bench: outputs of the last timed step -> %s (%s envs)\n'
+                   % (directory, nenv if keep is None else '%d of %d' % (len(keep), nenv)))
+
+
 def _progress(msg):
   """$DMC_BENCH_PROGRESS=1: stage markers on stderr (long legs: soccer)."""
   if os.environ.get('DMC_BENCH_PROGRESS'):
@@ -306,10 +343,18 @@ def _progress(msg):
 _T0 = time.time()
 
 
+def _positive(text):
+  n = int(text)
+  if n < 1:
+    raise argparse.ArgumentTypeError('must be at least 1')
+  return n
+
+
 def parse_args(argv=None):
   ap = argparse.ArgumentParser()
   ap.add_argument('--gpus', type=int, default=1)
-  ap.add_argument('--steps', type=int, default=1000)
+  ap.add_argument('--steps', type=_positive, default=1000,
+                  help='timed control steps')
   ap.add_argument('--warmup', type=int, default=50)
   ap.add_argument('--domain', default='cheetah')
   ap.add_argument('--task', default='run')
@@ -319,11 +364,18 @@ def parse_args(argv=None):
                   help='total envs, sharded over the GPUs (strong scaling only)')
   ap.add_argument('--precision', default='f32', choices=['f32', 'f64', 'mixed'],
                   help='mixed: fp32 arithmetic, qpos/qvel carried as fp64 (hi, lo) pairs')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also the CPU-oracle baseline and its error samples and the '
+                       'fp64 (tolerance-compliant) leg at N = 1, the humanoid-walk '
+                       'strong-scaling leg at N > 1')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='with --full: skip the CPU-oracle baseline and the fp64 leg')
   ap.add_argument('--no-compliant-leg', action='store_true',
-                  help='skip the short fp64 (tolerance-compliant) leg at N = 1')
+                  help='with --full: skip the short fp64 (tolerance-compliant) leg at N = 1')
   ap.add_argument('--no-strong-leg', action='store_true',
-                  help='skip the humanoid-walk strong-scaling leg at N > 1')
+                  help='with --full: skip the humanoid-walk strong-scaling leg at N > 1')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the outputs of the last timed step to DIR/<name>.npy')
   ap.add_argument('--dry-run', action='store_true',
                   help='launcher, sharding and gather only (gloo, no kernels)')
   return ap.parse_args(argv)
@@ -551,6 +603,8 @@ def main(argv=None):
       batch.read(wrapper.FIELD_RETURN).astype(np.float32)).to(dev)
   returns = distributed.gather_episode_returns(returns, total_envs)
   warn = batch.read(wrapper.FIELD_WARN)
+  if args.dump_outputs:
+    dump_outputs(batch, args.dump_outputs, '' if world == 1 else 'rank%d_' % rank)
 
   line = None
   if rank == 0:
@@ -617,7 +671,7 @@ def main(argv=None):
         'mean_episode_return': float(returns.mean().item()),
         'envs_with_warnings': int((warn != 0).sum()),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       line['cpu_baseline'] = cpu_baseline(
           args.domain, args.task, nsub, gpu_batch=batch,
           gpu_batch_model=physics.model,
@@ -629,8 +683,8 @@ def main(argv=None):
   # BASELINE's metric has two halves (throughput AND qpos within 1e-4 of the CPU
   # step over 1000 steps).  The fp64 build meets the second half for every env of
   # the smooth / planar-contact domains, so its figure rides in the same line.
-  if (world == 1 and args.precision != 'f64' and not args.no_compliant_leg
-      and not args.no_cpu_baseline):
+  if (world == 1 and args.full and args.precision != 'f64'
+      and not args.no_compliant_leg and not args.no_cpu_baseline):
     fsteps, fwarm = min(args.steps, 200), min(args.warmup, 20)
     if args.domain == 'soccer':
       # A second big-scratch code object in the same process inherits the first
@@ -665,7 +719,8 @@ def main(argv=None):
 
   # N > 1: BASELINE configs[3] in the same line (strong scaling: 8192 humanoids
   # in total, 1024 per GPU at N = 8)
-  if (world > 1 and args.global_batch is None and not args.no_strong_leg):
+  if (world > 1 and args.full and args.global_batch is None
+      and not args.no_strong_leg):
     _, stotal, _, sseeds = shard_of(args, world, rank, global_batch=8192)
     ssteps, swarm = min(args.steps, 200), min(args.warmup, 20)
     sf, senv = measure('humanoid', 'walk', args.precision, sseeds, local_rank,
@@ -707,7 +762,7 @@ def compliant_leg_in_a_child(args, steps, warmup):
   `tolerance_compliant` object built from the child's line."""
   cmd = [sys.executable, os.path.abspath(__file__), '--domain', args.domain, '--task', args.task,
          '--batch', str(args.batch), '--precision', 'f64', '--steps', str(steps),
-         '--warmup', str(warmup), '--no-compliant-leg']
+         '--warmup', str(warmup), '--full', '--no-compliant-leg']
   proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                         universal_newlines=True, env=_child_env())
   lines = [l for l in proc.stdout.splitlines() if l.startswith('{')]

@@ -1,11 +1,15 @@
 """Shared helpers for the parity tests (oracle = checker, HIP path = product)."""
 
+import json
 import os
 
 import numpy as np
 
 from dm_control_amd import codegen
 from dm_control_amd.mjcf import compiler
+from dm_control_amd.mjcf import model as mdl
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 TASKS = {'cartpole': codegen.TASK_CARTPOLE, 'cheetah': codegen.TASK_CHEETAH,
          'humanoid': codegen.TASK_HUMANOID, 'walker': codegen.TASK_WALKER,
@@ -26,6 +30,21 @@ def model_xml(name):
 
 def load_model(name):
   return compiler.from_xml_string(model_xml(name))
+
+
+def reference_model(name):
+  """The reference's MJCF file `name` as compiled by the in-tree compiler,
+  rebuilt from tests/golden/reference_models.json (make_golden.py): every
+  native field, body / joint / actuator names."""
+  with open(os.path.join(GOLDEN, 'reference_models.json')) as f:
+    rec = json.load(f)[name]
+  m = mdl.Model()
+  for field, kind in mdl.FIELDS:
+    v = rec['fields'][field]
+    setattr(m, field, v if kind in 'id' else
+            np.asarray(v, np.int32 if kind == 'I' else np.float64))
+  m.names = rec['names']
+  return m
 
 
 def initial_states(model, name, nenv, seed):

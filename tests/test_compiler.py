@@ -1,7 +1,6 @@
 """MJCF-subset compiler: derived checks that do not need libmujoco."""
 
 import math
-import os
 
 import numpy as np
 import pytest
@@ -13,8 +12,6 @@ from dm_control_amd.mjcf import compiler
 from dm_control_amd.mjcf import model as mdl
 from oracle import oracle
 
-REF_SUITE = '/root/reference/dm_control/suite'
-
 
 @pytest.mark.parametrize('name', ['cartpole', 'cheetah', 'humanoid', 'walker',
                                   'pendulum', 'acrobot', 'hopper', 'reacher',
@@ -22,11 +19,9 @@ REF_SUITE = '/root/reference/dm_control/suite'
 def test_in_tree_models_compile_like_the_reference_files(name):
   """The in-tree parameter tables (suite/models/*.py) give the same compiled
   model, names and ordering included, as the reference's MJCF files (which also
-  carry rendering includes, sites and sensors no task on the path reads)."""
-  path = os.path.join(REF_SUITE, name + '.xml')
-  if not os.path.exists(path):
-    pytest.skip('reference tree not present')
-  a = compiler.from_xml_path(path)
+  carry rendering includes, sites and sensors no task on the path reads),
+  recorded in tests/golden/reference_models.json."""
+  a = helpers.reference_model(name)
   b = helpers.load_model(name)
   skip = {'nsensor', 'nsensordata', 'sensor_type', 'sensor_objid',
           'sensor_adr', 'sensor_dim'}

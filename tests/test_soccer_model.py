@@ -2,7 +2,7 @@
 
 The frozen scenes of dm_control_amd/locomotion/models -- position-controlled
 CMU humanoid on a fixed pitch, and the regulation ball -- against the reference
-data where the tree is present (parameter tables vs humanoid_CMU_V2019.xml),
+data (parameter tables vs humanoid_CMU_V2019.xml, recorded under tests/golden),
 against closed forms (position actuators, weight on the floor, condim-6 /
 priority contact of the ball), and on the device against the oracle
 (`-m gpu`).  Stage 2 groundwork: scenes with several walkers (nv > 64) compile, generate a
@@ -10,8 +10,6 @@ kernel header (multi-word dof sets) and step on the oracle; the checks below
 are CPU-side.  Composer, observables, mocap initialiser and per-episode
 recompilation are not built.
 """
-
-import os
 
 import numpy as np
 import pytest
@@ -23,9 +21,6 @@ from dm_control_amd.locomotion.models import soccer
 from dm_control_amd.mjcf import compiler
 from oracle import oracle
 
-REF_XML = ('/root/reference/dm_control/locomotion/walkers/assets/'
-           'humanoid_CMU_V2019.xml')
-
 
 def _walker_model():
   return compiler.from_xml_string(soccer.build(1, with_ball=False))
@@ -35,9 +30,9 @@ def _ball_model():
   return compiler.from_xml_string(soccer.build(0, with_ball=True))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_XML), reason='reference tree absent')
 def test_tables_compile_like_the_reference_xml():
-  ref = compiler.from_xml_path(REF_XML)
+  """humanoid_CMU_V2019.xml as recorded in tests/golden/reference_models.json."""
+  ref = helpers.reference_model('humanoid_CMU_V2019')
   m = _walker_model()
   assert (m.nq, m.nv, m.nu) == (ref.nq + 7, ref.nv + 6, 56)
   for name in [b[0] for b in T.BODIES]:

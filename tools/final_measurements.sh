@@ -17,7 +17,7 @@ done
 cd $R
 for spec in "cheetah run 8192" "cheetah run 65536" "humanoid walk 8192" "humanoid walk 1024" "walker walk 8192" "cartpole swingup 4096" "hopper hop 8192" "hopper hop 4096" "acrobot swingup 8192" "reacher easy 8192" "point_mass easy 8192" "pendulum swingup 8192"; do
   set -- $spec
-  timeout -k 10 300 python bench.py --domain $1 --task $2 --batch $3 > $O/bench_$1_$2_b$3.json 2> $O/bench_$1_$2_b$3.err
+  timeout -k 10 300 python bench.py --full --domain $1 --task $2 --batch $3 > $O/bench_$1_$2_b$3.json 2> $O/bench_$1_$2_b$3.err
   tail -c 400 $O/bench_$1_$2_b$3.json | head -c 200; echo
 done
 cat $O/stats_*.json $O/pmc_*.json

@@ -20,7 +20,7 @@ cd $R
 cp $O/counters_*_b*.json $R/profiles/ 2>/dev/null   # so that the bench lines below carry them
 for spec in "cheetah run 8192 f32" "cheetah run 8192 f64" "cheetah run 65536 f32" "cheetah run 262144 f32" "cartpole swingup 4096 f32" "cartpole swingup 4096 f64" "cartpole swingup 4096 mixed" "humanoid walk 1024 f32" "humanoid walk 1024 f64" "humanoid walk 8192 f32" "walker walk 8192 f32" "hopper hop 8192 f32" "acrobot swingup 8192 f32" "reacher easy 8192 f32" "point_mass easy 8192 f32" "pendulum swingup 8192 f32"; do
   set -- $spec
-  timeout -k 10 400 python bench.py --domain $1 --task $2 --batch $3 --precision $4 > $O/bench_$1_$2_b$3_$4.json 2> $O/bench_$1_$2_b$3_$4.err || exit 1
+  timeout -k 10 400 python bench.py --full --domain $1 --task $2 --batch $3 --precision $4 > $O/bench_$1_$2_b$3_$4.json 2> $O/bench_$1_$2_b$3_$4.err || exit 1
   python3 -c "
 import json,sys
 d=json.loads([l for l in open('$O/bench_$1_$2_b$3_$4.json') if l.startswith('{')][-1])

@@ -23,7 +23,7 @@ done
 cp $R/gpurun_out/measure/counters_*.json $O/ 2>/dev/null
 cp $R/gpurun_out/measure/counters_*.json $R/profiles/ 2>/dev/null   # the default line below carries them
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 cut -c1-400 $O/bench_default.json
 find $O -name "*.csv" -size +2M -delete
 echo done

@@ -23,9 +23,9 @@ done
 cp $R/gpurun_out/measure/counters_*.json $O/ 2>/dev/null
 cp $R/gpurun_out/measure/counters_*.json $R/profiles/ 2>/dev/null   # the lines below carry them
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 cut -c1-400 $O/bench_default.json
-DMC_BENCH_PROGRESS=1 timeout -k 10 600 python bench.py --domain soccer --task 2v2 --batch 1024 --steps 30 --warmup 3 > $O/bench_soccer_2v2_b1024_f32.json 2> $O/bench_soccer_2v2_b1024_f32.err || { echo soccer bench failed; tail -8 $O/bench_soccer_2v2_b1024_f32.err; }
+DMC_BENCH_PROGRESS=1 timeout -k 10 600 python bench.py --full --domain soccer --task 2v2 --batch 1024 --steps 30 --warmup 3 > $O/bench_soccer_2v2_b1024_f32.json 2> $O/bench_soccer_2v2_b1024_f32.err || { echo soccer bench failed; tail -8 $O/bench_soccer_2v2_b1024_f32.err; }
 cut -c1-300 $O/bench_soccer_2v2_b1024_f32.json
 for q in loud quiet; do timeout -k 10 400 python tools/debug/pitch_profile.py $q --team > $O/pitch_stage_profile_team_$q.txt 2>&1; done
 timeout -k 10 300 python tools/debug/pitch_bench_profile.py solver > $O/pitch_bench_solver_profile.txt 2>&1

@@ -9,7 +9,7 @@ tail -3 $O/gputests.log
 grep OBSERVED $O/gputests.log > $O/observed.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 && tail -2 $O/smoke.log || { echo smoke failed; tail -5 $O/smoke.log; }
 timeout -k 10 600 python tools/spill_hazard/variants.py run > $O/spill_hazard_variants.txt 2>&1; cat $O/spill_hazard_variants.txt | cut -c1-400
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo bench failed; tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo bench failed; tail -5 $O/bench_default.err; exit 1; }
 python3 -c "
 import json
 d=json.loads([l for l in open('$O/bench_default.json') if l.startswith('{')][-1])

@@ -23,12 +23,12 @@ done
 cp $R/gpurun_out/measure/counters_*.json $O/ 2>/dev/null
 cp $R/gpurun_out/measure/counters_*.json $R/profiles/ 2>/dev/null   # so that the bench lines below carry them
 cd $R
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 for spec in "cheetah run 8192 f64" "cheetah run 65536 f32" "cheetah run 262144 f32" "cartpole swingup 4096 f32" "cartpole swingup 4096 f64" "cartpole swingup 4096 mixed" "humanoid walk 1024 f32" "humanoid walk 1024 f64" "humanoid walk 8192 f32" "walker walk 8192 f32" "walker walk 8192 f64" "hopper hop 8192 f32" "hopper hop 8192 f64"; do
   set -- $spec
-  timeout -k 10 400 python bench.py --domain $1 --task $2 --batch $3 --precision $4 --no-compliant-leg > $O/bench_$1_$2_b$3_$4.json 2> $O/bench_$1_$2_b$3_$4.err || exit 1
+  timeout -k 10 400 python bench.py --full --domain $1 --task $2 --batch $3 --precision $4 --no-compliant-leg > $O/bench_$1_$2_b$3_$4.json 2> $O/bench_$1_$2_b$3_$4.err || exit 1
 done
-timeout -k 10 900 python bench.py --domain soccer --task 2v2 --batch 1024 --steps 10 --warmup 2 --no-compliant-leg > $O/bench_soccer_2v2_b1024_f32.json 2> $O/bench_soccer_2v2_b1024_f32.err || { echo soccer bench failed; tail -5 $O/bench_soccer_2v2_b1024_f32.err; }
+timeout -k 10 900 python bench.py --full --domain soccer --task 2v2 --batch 1024 --steps 10 --warmup 2 --no-compliant-leg > $O/bench_soccer_2v2_b1024_f32.json 2> $O/bench_soccer_2v2_b1024_f32.err || { echo soccer bench failed; tail -5 $O/bench_soccer_2v2_b1024_f32.err; }
 python3 - <<PY
 import json,glob
 for f in sorted(glob.glob('$O/bench_*.json')):
