@@ -69,8 +69,10 @@ MAX_VGPR_SPILLS = 128
 MAX_SGPR_SPILLS = 128
 # The several-lanes kernel (csrc/dmc_coop.hip) keeps per-env data in LDS and its
 # uniform address arithmetic in SGPRs: every suite build spills 136-386 SGPRs
-# (to VGPR lanes, no scratch traffic) and at most 7 VGPRs, and all of them are
-# parity-tested per step against the oracle.  What the guard must refuse there
+# (to VGPR lanes, no scratch traffic) and at most 7 VGPRs, and every one that
+# `Physics` can select is parity-tested per step against the oracle
+# (tests/selection_matrix.py lists them; a CPU test keeps the list equal to the
+# policy, tests/test_gpu_selection.py runs each line).  What the guard must refuse there
 # is the same thing as above: builds that spill VGPRs wholesale to scratch
 # (the 62-dof soccer walker: 1652 fp32 / 6552 fp64).
 COOP_MAX_SGPR_SPILLS = 640
@@ -141,6 +143,16 @@ _COOP_OVERBUDGET_MSG = (
     'the several-lanes build of this model spills %%s (VGPR, SGPR) registers '
     '(budget %d / %d); set $DMC_ALLOW_OVERBUDGET=1 to build it anyway'
     % (MAX_VGPR_SPILLS, COOP_MAX_SGPR_SPILLS))
+
+
+class LdsWorkingSetError(ValueError, RuntimeError):
+  """`group` lanes per env put 64/group envs into one workgroup's LDS; this
+  model's working set times that many envs does not fit (the static_assert of
+  csrc/dmc_coop.hip).  A ValueError: the argument set cannot be built."""
+
+
+_LDS_MSG = ('%d lanes per env (%s): the working sets of the %d envs of a workgroup '
+            'do not fit in LDS; use a larger group or the one-env-per-lane kernel')
 
 
 def _allow_overbudget():
@@ -332,9 +344,18 @@ def build_model(model, task=codegen.TASK_NONE, precision='f32',
     flags += ('-DDMC_GROUP=%d' % min(group, 64), '-DDMC_COOP_DUO=%d' % (group == 128))
     out = os.path.join(_BUILD, 'dmc_%s.hsaco' % model_key(
         model, task, precision, ncon_max, flags, True))
+    if not force and os.path.exists(out + '.nolds'):
+      raise LdsWorkingSetError(_LDS_MSG % (group, precision, 64//min(group, 64)))
     if force or not os.path.exists(out):
-      spills = _compile(model, task, precision, ncon_max, flags, True, out,
-                        keep_temps, source='dmc_coop.hip')
+      try:
+        spills = _compile(model, task, precision, ncon_max, flags, True, out,
+                          keep_temps, source='dmc_coop.hip')
+      except RuntimeError as e:
+        if 'does not fit in LDS' not in str(e):
+          raise
+        with open(out + '.nolds', 'w') as f:    # refused without compiling next time
+          f.write('static_assert of csrc/dmc_coop.hip: ENV_WORDS*EPB*sizeof(real) > 150 KB\n')
+        raise LdsWorkingSetError(_LDS_MSG % (group, precision, 64//min(group, 64))) from None
       # the several-lanes kernel keeps its working set in LDS; a build that
       # spills beyond the budget is as untrusted as an over-budget unrolled one
       ok = _within_spill_budget(spills, COOP_MAX_SGPR_SPILLS)

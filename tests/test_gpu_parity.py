@@ -38,86 +38,13 @@ pytestmark = pytest.mark.gpu
 
 W = wrapper
 
-# fp32 teacher-forced per-step error (median, p99, max) asserted per model:
-# about 10x the values observed on MI355X (round 2, both kernels; observed
-# medians: cartpole 3.6e-8, cheetah 1.2e-7, humanoid 9.6e-7, walker 6.6e-7,
-# pendulum 3.5e-8, acrobot 4.3e-8, hopper 2.9e-7, reacher 1.1e-7, point_mass
-# 8.7e-9; observed maxima 1.1e-7 ... 1.2e-4, and 1.8e-3 for one humanoid sample
-# of the two-envs-per-wave build: the maximum is set by single steps in which
-# a constraint row sits within rounding of its activation threshold)
-FP32_PER_STEP = {
-    'cartpole': (4e-7, 1e-6, 2e-6), 'cheetah': (1.5e-6, 3e-5, 2e-4),
-    'humanoid': (1e-5, 1.5e-4, 5e-3), 'walker': (8e-6, 8e-5, 5e-4),
-    'pendulum': (4e-7, 1.2e-6, 2e-6), 'acrobot': (5e-7, 1.2e-6, 3e-6),
-    'hopper': (3e-6, 5e-5, 3e-4), 'reacher': (1.2e-6, 1.2e-5, 3e-5),
-    'point_mass': (1e-7, 2.5e-6, 2e-5)}
-
-
-def _assert_fp32_per_step(name, e):
-  med, p99, top = FP32_PER_STEP[name]
-  assert np.median(e) <= med, (name, np.median(e))
-  assert np.percentile(e, 99) <= p99, (name, np.percentile(e, 99))
-  assert e.max() <= top, (name, e.max())
-
-
-def _device_batch(model, task, precision, nenv, mode='auto', lds_budget=None,
-                  group=64):
-  hm = W.HipModel(build.build_model(model, task, precision, mode=mode,
-                                    lds_budget=lds_budget, group=group))
-  return hm, W.HipBatch(hm, nenv)
-
-
-def _oracle_envs(model, qpos, qvel):
-  om = oracle.OracleModel(model)
-  datas = [oracle.OracleData(om) for _ in range(len(qpos))]
-  for i, d in enumerate(datas):
-    d.qpos[:] = qpos[i]
-    d.qvel[:] = qvel[i]
-    d.step1()
-  return om, datas
-
-
-def _degenerate(d, model):
-  """True if a capsule-capsule contact has (numerically) intersecting axes."""
-  for c in range(d.ncon):
-    con = d.contact(c)
-    g1, g2 = con['geom1'], con['geom2']
-    if model.geom_type[g1] == 3 and model.geom_type[g2] == 3:
-      if con['dist'] < -(model.geom_size[g1, 0] + model.geom_size[g2, 0]) + 1e-4:
-        return True
-  return False
-
-
-def _teacher_forced(name, precision, nenv, steps, nsub, lds_budget=None,
-                    mode=None, group=64):
-  model = helpers.load_model(name)
-  hm, hb = _device_batch(model, helpers.TASKS[name], precision, nenv,
-                         mode or helpers.MODES[name], lds_budget, group)
-  qpos, qvel = helpers.initial_states(model, name, nenv, seed=7)
-  om, datas = _oracle_envs(model, qpos, qvel)
-  rs = np.random.RandomState(11)
-  errs = []
-  for _ in range(steps):
-    oq = np.array([d.qpos.copy() for d in datas])
-    ov = np.array([d.qvel.copy() for d in datas])
-    ow = np.array([d.qacc_warmstart.copy() for d in datas])
-    skip = np.array([_degenerate(d, model) for d in datas])
-    hb.set_state(oq.T, ov.T, ow.T)
-    ctrl = rs.uniform(-1, 1, (nenv, model.nu))
-    hb.step_host(ctrl, nsub)
-    q = hb.read(W.FIELD_QPOS).T.astype(np.float64)
-    v = hb.read(W.FIELD_QVEL).T.astype(np.float64)
-    for i, d in enumerate(datas):
-      d.ctrl[:] = ctrl[i]
-      for _ in range(nsub):
-        skip[i] |= _degenerate(d, model)
-        d.physics_step()
-    nq = np.array([d.qpos.copy() for d in datas])
-    nv = np.array([d.qvel.copy() for d in datas])
-    e = np.maximum(helpers.rel_err(q, nq), helpers.rel_err(v, nv))
-    errs.append(e[~skip])
-  assert not hb.read(W.FIELD_WARN).any()
-  return np.concatenate(errs)
+# moved to tests/helpers.py (shared with tests/test_gpu_selection.py)
+FP32_PER_STEP = helpers.FP32_PER_STEP
+_assert_fp32_per_step = helpers._assert_fp32_per_step   # pylint: disable=protected-access
+_device_batch = helpers._device_batch                   # pylint: disable=protected-access
+_oracle_envs = helpers._oracle_envs                     # pylint: disable=protected-access
+_degenerate = helpers._degenerate                       # pylint: disable=protected-access
+_teacher_forced = helpers._teacher_forced               # pylint: disable=protected-access
 
 
 @pytest.mark.parametrize('name,nsub', [('cartpole', 1), ('cheetah', 1),
@@ -164,10 +91,9 @@ def test_several_lanes_per_env_build_matches_oracle(name, nsub, group):
   (group 32), and with the second wavefront that builds the constraint rows
   and factorises M + h D meanwhile (group 128, the humanoid's fp32 default).
   Odd batch: the last workgroup is partially filled."""
-  if group >= 64:
-    e = _teacher_forced(name, 'f64', nenv=33, steps=10, nsub=nsub, mode='coop',
-                        group=group)
-    assert e.max() <= 1e-9, e.max()
+  e = _teacher_forced(name, 'f64', nenv=33, steps=10, nsub=nsub, mode='coop',
+                      group=group)
+  assert e.max() <= 1e-9, e.max()
   e = _teacher_forced(name, 'f32', nenv=65, steps=10, nsub=nsub, mode='coop',
                       group=group)
   print('OBSERVED fp32 per-step coop %s G=%d: median %.2e p99 %.2e max %.2e'

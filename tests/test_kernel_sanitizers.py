@@ -190,7 +190,15 @@ def _build_coop(model, task, tmp_path, sanitizer, group):
     ('humanoid', 'thread', 128, 9),
     ('hopper', 'thread', 128, 10),
     ('humanoid', 'address,undefined', 128, 9),
-    ('stacked_boxes', 'address,undefined', 64, 30)])
+    ('stacked_boxes', 'address,undefined', 64, 30),
+    # 8 and 16 lanes per env (eight / four envs per wavefront): the G < 32
+    # branches of the group broadcast and of the row reductions (the shim is an
+    # fp64 build: the cheetah's 8-lane fp64 shape is the one `build_model`
+    # refuses for its LDS size, tests/test_selection.py, so it runs with 16)
+    ('cheetah', 'thread', 16, 12),
+    ('hopper', 'address,undefined', 16, 12),
+    ('walker', 'thread', 16, 8),
+    ('walker', 'address,undefined', 8, 8)])
 def test_several_lanes_per_env_source(name, sanitizer, group, steps, tmp_path):
   """csrc/dmc_coop.hip with one thread per lane (tests/host_shim/shim_coop.h):
   a phase hand-over is a pthread barrier, so ThreadSanitizer reports any LDS
