@@ -3,8 +3,22 @@
 Everything is built IN-TREE (csrc/libdmc_hip.so, csrc/_build/<key>.hsaco) so
 the artefacts travel to the GPU box with the repository snapshot.  hipcc
 cross-compiles for gfx950 without a GPU present.
+
+`build_model(...)` is `realise(spec(...))`.  `spec` checks the arguments and
+resolves them, touching no file, into source, compile precision, -D flags and
+the tiers the request may use; `_flags` alone writes the compiler's command line.
+The ladder: unrolled, "semi" (generic source, backend unroller on; small models)
+and strictly rolled for "auto", the last two for "rolled" / "team", the first
+for "unrolled"; "coop" is one tier on csrc/dmc_coop.hip.  Each code object has
+one sidecar record, `<key>.hsaco.verdict`: "ok", "over" (budget) or "nolds" (does
+not fit in LDS), with the spill counts.  `realise` takes a tier's verdict from
+the record, or compiles to `.tmp`, records, and only then publishes
+(os.replace); it returns the first "ok" tier, falls through, raises at the
+last.  "over" is returned only as the last tier of a request made under
+`allow_overbudget()`; a file without a record never is.
 """
 
+import collections
 import contextlib
 import hashlib
 import os
@@ -76,7 +90,7 @@ MAX_SGPR_SPILLS = 128
 # is the same thing as above: builds that spill VGPRs wholesale to scratch
 # (the 62-dof soccer walker: 1652 fp32 / 6552 fp64).
 COOP_MAX_SGPR_SPILLS = 640
-SEMI_ROLLED_MAX_NV = 16     # see build_model: the generic tier with the backend unroller on
+SEMI_ROLLED_MAX_NV = 16     # see _SEMI: the generic tier with the backend unroller on
 
 
 # fp32 builds: v_rcp / v_rsq based division and sqrt (<= 2.5 ulp) instead of the
@@ -144,6 +158,11 @@ _COOP_OVERBUDGET_MSG = (
     '(budget %d / %d); set $DMC_ALLOW_OVERBUDGET=1 to build it anyway'
     % (MAX_VGPR_SPILLS, COOP_MAX_SGPR_SPILLS))
 
+_ROLLED_OVERBUDGET_MSG = (
+    'the rolled build of this model spills %%s (VGPR, SGPR) registers (budget '
+    '%d / %d); set $DMC_ALLOW_OVERBUDGET=1 to build it anyway'
+    % (MAX_VGPR_SPILLS, COOP_MAX_SGPR_SPILLS))
+
 
 class LdsWorkingSetError(ValueError, RuntimeError):
   """`group` lanes per env put 64/group envs into one workgroup's LDS; this
@@ -175,68 +194,160 @@ def allow_overbudget():
       os.environ['DMC_ALLOW_OVERBUDGET'] = prev
 
 
-def _within_spill_budget(spills, max_sgpr=MAX_SGPR_SPILLS):
+def _within_spill_budget(spills, max_sgpr):
   return (spills is not None and spills[0] <= MAX_VGPR_SPILLS
           and spills[1] <= max_sgpr)
 
 
-def _compile(model, task, precision, ncon_max, extra_flags, unroll, out,
-             keep_temps, source='dmc_kernels.hip', kernel='dmc_step'):
-  key = os.path.basename(out)[4:-6]
+# One tier: `unroll` as model_key takes it (True: the unrolled source; "semi" /
+# False: the generic one), the SGPR spill budget within which it is trusted,
+# and what it says beyond that budget as the last tier of a request.
+Tier = collections.namedtuple('Tier', 'unroll max_sgpr refusal')
+_UNROLLED = Tier(True, MAX_SGPR_SPILLS, _OVERBUDGET_MSG)
+# Generic ("rolled") source, two tiers.  First with the backend's loop unroller
+# left on: for small models it turns the per-lane loops back into mostly
+# straight-line code within the spill budget (cheetah fp64: 14 VGPR / 300 SGPR
+# spills, 0.33 ms per launch against 1.33 ms strictly rolled).  Beyond the
+# budget -- mid-size models: humanoid fp64 3644, the 62-dof walker 14591 spilled
+# VGPRs -- the strictly rolled form (-fno-unroll-loops: no spills at all).
+# Only small models take the first: it is the regime every GPU parity test of
+# a suite fp64 build covers, and the one time the unroller was let loose on a
+# big model (the 2v2 pitch) it produced wrong code (csrc/dmc_kernels.hip,
+# DMC_KEEP_ROLLED).
+_SEMI = Tier('semi', COOP_MAX_SGPR_SPILLS, None)
+_ROLLED = Tier(False, COOP_MAX_SGPR_SPILLS, _ROLLED_OVERBUDGET_MSG)
+# the several-lanes kernel keeps its working set in LDS; a build that spills
+# beyond the budget is as untrusted as an over-budget unrolled one
+_COOP = Tier(True, COOP_MAX_SGPR_SPILLS, _COOP_OVERBUDGET_MSG)
+
+# What `build_model` was asked (model .. lds_budget, as given) and what that
+# means: source file, compile precision, final -D flags, tiers in order.
+Spec = collections.namedtuple(
+    'Spec', 'model task ncon_max precision mode group lds_budget source real flags tiers')
+
+
+def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group):
+  """Checks the arguments of `build_model` and resolves them into a `Spec`.
+  Pure: reads the environment, touches no file and starts no process."""
+  if precision not in ('f32', 'f64', 'mixed'):
+    raise ValueError('precision must be "f32", "f64" or "mixed"')
+  if mode not in ('auto', 'unrolled', 'rolled', 'coop', 'team'):
+    raise ValueError('mode must be auto, unrolled, rolled, coop or team')
+  if precision == 'mixed' and mode in ('coop', 'team'):
+    raise ValueError('precision "mixed" is built for the one-env-per-lane kernel')
+  if extra_flags is None:
+    # experiment hook: extra -D flags for ablation builds (never set in tests)
+    extra_flags = os.environ.get('DMC_EXTRA_FLAGS', '').split()
+  flags = tuple(extra_flags)
+  if mode == 'team':
+    # big scenes: the generic source with one wavefront per env (csrc/dmc_kernels.hip,
+    # "team mode"): matrices, rows and contacts in the HBM workspace, a tree's
+    # diagonal block at a time in LDS
+    flags += ('-DDMC_TEAM=64',)
+  if precision == 'mixed':
+    # fp32 arithmetic, qpos/qvel carried between steps as fp64 (high, low)
+    # pairs (csrc/dmc_kernels.hip, DMC_STATE_COMP); one-env-per-lane kernel only
+    flags += ('-DDMC_STATE_COMP=1',)
+  if mode == 'coop':
+    # several lanes per env (csrc/dmc_coop.hip): working set in LDS, generic
+    # loops; `lds_budget` does not apply (no row tiers)
+    flags = tuple(f for f in flags if not f.startswith('-DDMC_LDS_BUDGET'))
+    if group not in (8, 16, 32, 64, 128):
+      raise ValueError('group must be 8, 16, 32, 64 or 128 (two wavefronts) lanes per env')
+    # 128: one env per 64 lanes plus a second wavefront that builds the
+    # constraint rows and factorises M + h D meanwhile (Euler models; the best
+    # shape while the batch fits the chip in one round, 4 envs per CU)
+    flags += ('-DDMC_GROUP=%d' % min(group, 64), '-DDMC_COOP_DUO=%d' % (group == 128))
+    source, tiers = 'dmc_coop.hip', (_COOP,)
+  else:
+    if lds_budget is not None and lds_budget != 128*1024:
+      flags += ('-DDMC_LDS_BUDGET=%d' % lds_budget,)
+    semi = (model.nv <= SEMI_ROLLED_MAX_NV     # (experiments: skip this tier)
+            and os.environ.get('DMC_ROLLED_STRICT') != '1')
+    tiers = (_SEMI, _ROLLED) if semi else (_ROLLED,)
+    if mode in ('auto', 'unrolled'):
+      tiers = (_UNROLLED,) + tiers if mode == 'auto' else (_UNROLLED,)
+    source = 'dmc_kernels.hip'
+  return Spec(model, task, ncon_max, precision, mode, group, lds_budget, source,
+              'f64' if precision == 'f64' else 'f32', flags, tiers)
+
+
+def _flags(spec_, tier, remarks=False):
+  """The compiler flags of one tier of `spec_`: the only place that knows them
+  (hipcc, the in-process route and `code_object_bytes` all come here).
+  `remarks`: have the resource usage reported, for `_spills`.  The order is
+  part of the result: clang hashes its command line into the code object.
+
+  -pragma-unroll-threshold: the per-model straight-line code is far beyond
+    LLVM's default budget; without it the pair loop stays rolled, per-lane
+    arrays are indexed dynamically and the whole working set lands in scratch.
+  -fno-slp-vectorize: v_pk_*_f32 is not faster on gfx950 and the packing
+    moves cost ~25 % extra instructions plus spills.
+  -fno-hip-fp32-correctly-rounded-divide-sqrt (fp32 build only): v_rcp/v_rsq
+    based division and sqrt (<= 2.5 ulp) instead of the 10-instruction
+    IEEE sequences; the fp64 build keeps exact division.
+  -ffinite-math-only -fno-signed-zeros: lets LLVM fold 0*x and x+0.  In the
+    unrolled build the world frame, joint axes and body offsets are
+    constants, so for the planar suite models (cheetah, walker, hopper,
+    cart-pole, ...) the y components, two quaternion entries and four matrix
+    entries of every frame are exact zeros that now disappear at compile time
+    (cheetah: 25.4 k -> 18.6 k VALU instructions per step).  Values are
+    unchanged for finite inputs; NaN/inf detection is done on bit patterns
+    (`bad()` in the kernel source), not with comparisons.
+  """
+  f64 = spec_.real == 'f64'
+  flags = ['-DDMC_REAL_IS_DOUBLE'] if f64 else list(_FP32_FLAGS)
+  flags += list(spec_.flags) + [
+      '--offload-arch=' + ARCH, '-O3', '-std=c++17',
+      '-ffinite-math-only', '-fno-signed-zeros'] + (
+          ['-Rpass-analysis=kernel-resource-usage'] if remarks else []) + [
+      '-mllvm', '-pragma-unroll-threshold=%s' % os.environ.get(
+          'DMC_PRAGMA_UNROLL_THRESHOLD', '10000000'), '-fno-slp-vectorize',
+      '-ffp-contract=off' if f64 else '-ffp-contract=fast']
+  if tier.unroll is False:   # ("semi": generic source, the backend may unroll)
+    flags += list(_ROLLED_FLAGS)
+  return flags
+
+
+def _key(spec_, tier):
+  return model_key(spec_.model, spec_.task, spec_.real, spec_.ncon_max,
+                   spec_.flags, tier.unroll)
+
+
+def _compile(spec_, tier, out, keep_temps):
+  """Compiles one tier of `spec_` to `out + '.tmp'` (header and temporaries next
+  to it); returns its (vgpr, sgpr) spill counts, see `_spills`."""
+  model = spec_.model
   if os.environ.get('DMC_BUILD_LOG'):     # which code objects were not pre-built
     with open(os.environ['DMC_BUILD_LOG'], 'a') as f:
       f.write('%s task=%d %s ncon_max=%r flags=%r unroll=%r nv=%d nbody=%d\n' % (
-          source, task, precision, ncon_max, tuple(extra_flags), unroll, model.nv, model.nbody))
-  header = os.path.join(_BUILD, 'model_%s.h' % key)
+          spec_.source, spec_.task, spec_.real, spec_.ncon_max, spec_.flags,
+          tier.unroll, model.nv, model.nbody))
+  header = os.path.join(os.path.dirname(out), 'model_%s.h' % _key(spec_, tier))
+  text = codegen.generate_header(model, spec_.task, spec_.ncon_max,
+                                 unroll=tier.unroll is True)
   with open(header, 'w') as f:
-    f.write(codegen.generate_header(model, task, ncon_max, unroll=unroll is True))
-  # -pragma-unroll-threshold: the per-model straight-line code is far beyond
-  #   LLVM's default budget; without it the pair loop stays rolled, per-lane
-  #   arrays are indexed dynamically and the whole working set lands in scratch.
-  # -fno-slp-vectorize: v_pk_*_f32 is not faster on gfx950 and the packing
-  #   moves cost ~25 % extra instructions plus spills.
-  # -fno-hip-fp32-correctly-rounded-divide-sqrt (fp32 build only): v_rcp/v_rsq
-  #   based division and sqrt (<= 2.5 ulp) instead of the 10-instruction
-  #   IEEE sequences; the fp64 build keeps exact division.
-  # -ffinite-math-only -fno-signed-zeros: lets LLVM fold 0*x and x+0.  In the
-  #   unrolled build the world frame, joint axes and body offsets are
-  #   constants, so for the planar suite models (cheetah, walker, hopper,
-  #   cart-pole, ...) the y components, two quaternion entries and four matrix
-  #   entries of every frame are exact zeros that now disappear at compile time
-  #   (cheetah: 25.4 k -> 18.6 k VALU instructions per step).  Values are
-  #   unchanged for finite inputs; NaN/inf detection is done on bit patterns
-  #   (`bad()` in the kernel source), not with comparisons.
-  flags = ['--offload-arch=' + ARCH, '-O3', '-std=c++17',
-           '-ffinite-math-only', '-fno-signed-zeros',
-           '-Rpass-analysis=kernel-resource-usage',
-           '-mllvm', '-pragma-unroll-threshold=%s' % os.environ.get(
-               'DMC_PRAGMA_UNROLL_THRESHOLD', '10000000'), '-fno-slp-vectorize',
-           '-ffp-contract=off' if precision == 'f64' else '-ffp-contract=fast']
-  flags[0:0] = list(extra_flags)
-  flags[0:0] = ['-DDMC_REAL_IS_DOUBLE'] if precision == 'f64' else list(_FP32_FLAGS)
-  if unroll is False:      # (unroll == 'semi': generic source, the backend may unroll)
-    flags += list(_ROLLED_FLAGS)
+    f.write(text)
+  flags = _flags(spec_, tier, remarks=True)
   if backend() == 'hiprtc':
-    with open(header) as f:
-      code, log = _compile_in_process(f.read(), source, flags)
+    code, log = _compile_in_process(text, spec_.source, flags)
     with open(out + '.tmp', 'wb') as f:
       f.write(code)
+  else:
+    cmd = [_hipcc(), '--genco'] + flags + [
+        '-DDMC_MODEL_HEADER="%s"' % header, '-I', _CSRC,
+        '-o', out + '.tmp', os.path.join(_CSRC, spec_.source)]
     if keep_temps:
-      print(log)
-    return _spills(log, kernel)
-  cmd = [_hipcc(), '--genco'] + flags + [
-      '-DDMC_MODEL_HEADER="%s"' % header, '-I', _CSRC,
-      '-o', out + '.tmp', os.path.join(_CSRC, source)]
+      cmd.insert(1, '-save-temps')
+    proc = subprocess.run(cmd, cwd=os.path.dirname(out), stdout=subprocess.PIPE,
+                          stderr=subprocess.STDOUT, universal_newlines=True)
+    if proc.returncode != 0:
+      raise RuntimeError('hipcc failed for model kernels:\n%s'
+                         % proc.stdout[-4000:])
+    log = proc.stdout
   if keep_temps:
-    cmd.insert(1, '-save-temps')
-  proc = subprocess.run(cmd, cwd=_BUILD, stdout=subprocess.PIPE,
-                        stderr=subprocess.STDOUT, universal_newlines=True)
-  if proc.returncode != 0:
-    raise RuntimeError('hipcc failed for model kernels:\n%s'
-                       % proc.stdout[-4000:])
-  if keep_temps:
-    print(proc.stdout)
-  return _spills(proc.stdout, kernel)
+    print(log)
+  return _spills(log)
 
 
 def _compile_in_process(header_text, source, flags):
@@ -261,20 +372,11 @@ def code_object_bytes(model, task=codegen.TASK_NONE, precision='f32',
   files): the `mj_loadXML` route for a model that was not pre-built --
   `wrapper.HipModel.from_code(build.code_object_bytes(model))`.  The generic
   (rolled) build by default: it compiles in seconds for any model size."""
-  flags = (['-DDMC_REAL_IS_DOUBLE'] if precision == 'f64' else list(_FP32_FLAGS)) + [
-           '--offload-arch=' + ARCH, '-O3', '-std=c++17', '-ffinite-math-only',
-           '-fno-signed-zeros', '-mllvm', '-pragma-unroll-threshold=10000000',
-           '-fno-slp-vectorize',
-           '-ffp-contract=off' if precision == 'f64' else '-ffp-contract=fast']
-  source = 'dmc_kernels.hip'
-  if coop_group:
-    flags += ['-DDMC_GROUP=%d' % min(coop_group, 64),
-              '-DDMC_COOP_DUO=%d' % (coop_group == 128)]
-    source, unroll = 'dmc_coop.hip', True
-  if not unroll:
-    flags += list(_ROLLED_FLAGS)
-  header = codegen.generate_header(model, task, ncon_max, unroll=unroll)
-  return _compile_in_process(header, source, flags)[0]
+  mode = 'coop' if coop_group else 'unrolled' if unroll else 'rolled'
+  spec_ = spec(model, task, precision, ncon_max, (), mode, None, coop_group or 64)
+  tier = spec_.tiers[-1]        # no spill counts on this route: strictly rolled
+  header = codegen.generate_header(model, task, ncon_max, unroll=tier.unroll is True)
+  return _compile_in_process(header, spec_.source, _flags(spec_, tier))[0]
 
 
 def lds_budget_for(nenv):
@@ -293,6 +395,58 @@ def lds_budget_for(nenv):
   return 36*1024            # 4 per CU: one wave on every SIMD
 
 
+def _recorded(out):
+  """The verdict on record for the code object `out`, from its sidecar file:
+  ("ok" | "over" | "nolds", spill counts as text), or (None, None)."""
+  try:
+    with open(out + '.verdict') as f:
+      verdict, _, counts = f.read().strip().partition(' ')
+  except FileNotFoundError:
+    return None, None
+  return (verdict, counts) if verdict in ('ok', 'over', 'nolds') else (None, None)
+
+
+def _accepted(verdict, last):
+  """Within budget; beyond it only as the last tier of a request made under
+  `allow_overbudget()` -- never as a step of "auto"."""
+  return verdict == 'ok' or (verdict == 'over' and last and _allow_overbudget())
+
+
+def realise(spec_, force=False, keep_temps=False):
+  """Walks the tiers of `spec_` (module docstring, "The ladder") and returns the
+  path of the first code object whose verdict is accepted.  `force`: ignore the
+  verdicts on record, i.e. compile every tier visited again."""
+  os.makedirs(_BUILD, exist_ok=True)
+  for tier in spec_.tiers:
+    last = tier is spec_.tiers[-1]
+    out = os.path.join(_BUILD, 'dmc_%s.hsaco' % _key(spec_, tier))
+    verdict, counts = (None, None) if force else _recorded(out)
+    if verdict is None or (_accepted(verdict, last) and not os.path.exists(out)):
+      try:
+        spills = _compile(spec_, tier, out, keep_temps)
+      except RuntimeError as e:
+        if 'does not fit in LDS' not in str(e):
+          raise
+        # static_assert of csrc/dmc_coop.hip: ENV_WORDS*EPB*sizeof(real) > 150 KB
+        verdict, counts = 'nolds', ''
+      else:
+        verdict = 'ok' if _within_spill_budget(spills, tier.max_sgpr) else 'over'
+        counts = '%r' % (spills,)
+      with open(out + '.verdict', 'w') as f:
+        f.write('%s %s\n' % (verdict, counts))
+      if _accepted(verdict, last):
+        os.replace(out + '.tmp', out)
+      elif verdict != 'nolds':
+        os.remove(out + '.tmp')
+    if verdict == 'nolds':
+      raise LdsWorkingSetError(_LDS_MSG % (
+          spec_.group, spec_.real, 64//min(spec_.group, 64)))
+    if _accepted(verdict, last):
+      return out
+    if last:
+      raise RuntimeError(tier.refusal % counts)
+
+
 def build_model(model, task=codegen.TASK_NONE, precision='f32',
                 ncon_max=None, force=False, keep_temps=False, extra_flags=None,
                 mode='auto', lds_budget=None, group=64):
@@ -307,141 +461,5 @@ def build_model(model, task=codegen.TASK_NONE, precision='f32',
   nv ~ 20+ models and for small shards; 128 = 64 lanes + a helper wavefront).  Returns the path of the gfx950 code
   object; cached in-tree by content hash.
   """
-  if precision not in ('f32', 'f64', 'mixed'):
-    raise ValueError('precision must be "f32", "f64" or "mixed"')
-  if mode not in ('auto', 'unrolled', 'rolled', 'coop', 'team'):
-    raise ValueError('mode must be auto, unrolled, rolled, coop or team')
-  if extra_flags is None:
-    # experiment hook: extra -D flags for ablation builds (never set in tests)
-    extra_flags = tuple(os.environ.get('DMC_EXTRA_FLAGS', '').split())
-  if mode == 'team':
-    # big scenes: the generic source with one wavefront per env (csrc/dmc_kernels.hip,
-    # "team mode"): matrices, rows and contacts in the HBM workspace, a tree's
-    # diagonal block at a time in LDS
-    if precision == 'mixed':
-      raise ValueError('precision "mixed" is built for the one-env-per-lane kernel')
-    extra_flags = tuple(extra_flags) + ('-DDMC_TEAM=64',)
-    mode = 'rolled'
-  if precision == 'mixed':
-    # fp32 arithmetic, qpos/qvel carried between steps as fp64 (high, low)
-    # pairs (csrc/dmc_kernels.hip, DMC_STATE_COMP); one-env-per-lane kernel only
-    if mode == 'coop':
-      raise ValueError('precision "mixed" is built for the one-env-per-lane kernel')
-    precision = 'f32'
-    extra_flags = tuple(extra_flags) + ('-DDMC_STATE_COMP=1',)
-  if lds_budget is not None and lds_budget != 128*1024:
-    extra_flags = tuple(extra_flags) + ('-DDMC_LDS_BUDGET=%d' % lds_budget,)
-  os.makedirs(_BUILD, exist_ok=True)
-  if mode == 'coop':
-    # several lanes per env (csrc/dmc_coop.hip): working set in LDS, generic
-    # loops; `lds_budget` does not apply (no row tiers)
-    flags = tuple(f for f in extra_flags if not f.startswith('-DDMC_LDS_BUDGET'))
-    if group not in (8, 16, 32, 64, 128):
-      raise ValueError('group must be 8, 16, 32, 64 or 128 (two wavefronts) lanes per env')
-    # 128: one env per 64 lanes plus a second wavefront that builds the
-    # constraint rows and factorises M + h D meanwhile (Euler models; the best
-    # shape while the batch fits the chip in one round, 4 envs per CU)
-    flags += ('-DDMC_GROUP=%d' % min(group, 64), '-DDMC_COOP_DUO=%d' % (group == 128))
-    out = os.path.join(_BUILD, 'dmc_%s.hsaco' % model_key(
-        model, task, precision, ncon_max, flags, True))
-    if not force and os.path.exists(out + '.nolds'):
-      raise LdsWorkingSetError(_LDS_MSG % (group, precision, 64//min(group, 64)))
-    if force or not os.path.exists(out):
-      try:
-        spills = _compile(model, task, precision, ncon_max, flags, True, out,
-                          keep_temps, source='dmc_coop.hip')
-      except RuntimeError as e:
-        if 'does not fit in LDS' not in str(e):
-          raise
-        with open(out + '.nolds', 'w') as f:    # refused without compiling next time
-          f.write('static_assert of csrc/dmc_coop.hip: ENV_WORDS*EPB*sizeof(real) > 150 KB\n')
-        raise LdsWorkingSetError(_LDS_MSG % (group, precision, 64//min(group, 64))) from None
-      # the several-lanes kernel keeps its working set in LDS; a build that
-      # spills beyond the budget is as untrusted as an over-budget unrolled one
-      ok = _within_spill_budget(spills, COOP_MAX_SGPR_SPILLS)
-      if not ok and not _allow_overbudget():
-        os.remove(out + '.tmp')
-        raise RuntimeError(_COOP_OVERBUDGET_MSG % (spills,))
-      os.replace(out + '.tmp', out)
-      with open(out + ('.ok' if ok else '.overbudget'), 'w') as f:
-        f.write('%r' % (spills,))
-    elif os.path.exists(out + '.overbudget') and not _allow_overbudget():
-      with open(out + '.overbudget') as f:
-        raise RuntimeError(_COOP_OVERBUDGET_MSG % f.read().strip())
-    return out
-
-  def path(unroll):
-    return os.path.join(_BUILD, 'dmc_%s.hsaco' % model_key(
-        model, task, precision, ncon_max, extra_flags, unroll))
-  marker = path(True) + '.rolled'     # "auto" decided against the unrolled build
-  vetted = path(True) + '.ok'         # spill counts recorded and within budget
-  if not force:
-    if mode != 'rolled' and os.path.exists(path(True)) and (
-        os.path.exists(vetted) or (mode == 'unrolled' and _allow_overbudget())):
-      return path(True)
-    over = path(True) + '.overbudget'   # built once with the override: spills known
-    if mode == 'unrolled' and os.path.exists(over) and not _allow_overbudget():
-      with open(over) as f:
-        raise RuntimeError(_OVERBUDGET_MSG % f.read().strip())
-  # `auto` decided against the unrolled build earlier (marker): straight to the
-  # generic tiers
-  skip_unrolled = mode == 'rolled' or (mode == 'auto' and not force
-                                       and os.path.exists(marker))
-  if not skip_unrolled:
-    out = path(True)
-    spills = _compile(model, task, precision, ncon_max, extra_flags, True, out,
-                      keep_temps)
-    ok = _within_spill_budget(spills)
-    if mode == 'unrolled' and not ok and not _allow_overbudget():
-      os.remove(out + '.tmp')
-      raise RuntimeError(_OVERBUDGET_MSG % (spills,))
-    if mode == 'unrolled' or ok:
-      os.replace(out + '.tmp', out)
-      if not ok:
-        with open(out + '.overbudget', 'w') as f:
-          f.write('%r' % (spills,))
-      if ok:
-        with open(vetted, 'w') as f:
-          f.write('vgpr spills %d, sgpr spills %d\n' % spills)
-      return out
-    os.remove(out + '.tmp')
-    with open(marker, 'w') as f:
-      f.write('spills (vgpr, sgpr): %r\n' % (spills,))
-  # Generic ("rolled") source, two tiers.  First with the backend's loop unroller
-  # left on: for small models it turns the per-lane loops back into mostly
-  # straight-line code within the spill budget (cheetah fp64: 14 VGPR / 300 SGPR
-  # spills, 0.33 ms per launch against 1.33 ms strictly rolled).  Beyond the
-  # budget -- mid-size models: humanoid fp64 3644, the 62-dof walker 14591 spilled
-  # VGPRs -- the strictly rolled form (-fno-unroll-loops: no spills at all).
-  # Only small models take this tier: it is the regime every GPU parity test of
-  # a suite fp64 build covers, and the one time the unroller was let loose on a
-  # big model (the 2v2 pitch) it produced wrong code (csrc/dmc_kernels.hip,
-  # DMC_KEEP_ROLLED).
-  semi = path('semi')
-  if (not force and not os.path.exists(semi + '.strict') and model.nv <= SEMI_ROLLED_MAX_NV
-      and os.environ.get('DMC_ROLLED_STRICT') != '1'):   # (experiments: skip this tier)
-    if os.path.exists(semi) and os.path.exists(semi + '.ok'):
-      return semi
-    spills = _compile(model, task, precision, ncon_max, extra_flags, 'semi', semi,
-                      keep_temps)
-    if _within_spill_budget(spills, COOP_MAX_SGPR_SPILLS):
-      os.replace(semi + '.tmp', semi)
-      with open(semi + '.ok', 'w') as f:
-        f.write('%r' % (spills,))
-      return semi
-    os.remove(semi + '.tmp')
-    with open(semi + '.strict', 'w') as f:
-      f.write('spills (vgpr, sgpr) with the loop unroller on: %r\n' % (spills,))
-  out = path(False)
-  if not force and os.path.exists(out):
-    return out
-  spills = _compile(model, task, precision, ncon_max, extra_flags, False, out,
-                    keep_temps)
-  if not _within_spill_budget(spills, COOP_MAX_SGPR_SPILLS) and not _allow_overbudget():
-    os.remove(out + '.tmp')
-    raise RuntimeError(
-        'the rolled build of this model spills %r (VGPR, SGPR) registers (budget '
-        '%d / %d); set $DMC_ALLOW_OVERBUDGET=1 to build it anyway'
-        % (spills, MAX_VGPR_SPILLS, COOP_MAX_SGPR_SPILLS))
-  os.replace(out + '.tmp', out)
-  return out
+  return realise(spec(model, task, precision, ncon_max, extra_flags, mode,
+                      lds_budget, group), force, keep_temps)

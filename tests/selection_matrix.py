@@ -22,7 +22,7 @@ test_soccer_load_other_team_sizes_match_oracle) and
 tests/test_soccer_task.py.
 """
 
-import contextlib
+from unittest import mock
 
 from dm_control_amd import build
 from dm_control_amd import engine
@@ -138,30 +138,17 @@ SMALL_GROUPS_REFUSED = (('cheetah', 8, 'f64'),)
 
 
 class _Recorded(Exception):
-  """Raised in place of the compile: the selection has been recorded."""
+  """Raised in place of the compile; `args[0]` is the spec that was asked for."""
 
 
-@contextlib.contextmanager
-def recording(calls):
-  """Inside, `build.build_model` appends its (precision, mode, group,
-  lds_budget) to `calls`, validates its arguments as the product does (the
-  real function runs up to its first `model_key` call, which comes after every
-  argument check and before any file is written) and raises `_Recorded`
-  instead of compiling."""
-  real_build, real_key = build.build_model, build.model_key
+def _refuse_to_compile(spec, force=False, keep_temps=False):
+  raise _Recorded(spec)
 
-  def model_key(*args, **kwargs):
-    raise _Recorded()
 
-  def build_model(model, task=0, precision='f32', ncon_max=None, **kwargs):
-    calls.append((precision, kwargs.get('mode', 'auto'), kwargs.get('group', 64),
-                  kwargs.get('lds_budget')))
-    return real_build(model, task, precision, ncon_max, **kwargs)
-  build.build_model, build.model_key = build_model, model_key
-  try:
-    yield
-  finally:
-    build.build_model, build.model_key = real_build, real_key
+def recording():
+  """Inside, `build.realise` raises `_Recorded` with the spec it receives
+  instead of compiling; `build.spec` has checked the arguments by then."""
+  return mock.patch.object(build, 'realise', _refuse_to_compile)
 
 
 def _subclasses(cls):
@@ -187,25 +174,20 @@ def first_task(domain):
 def select(domain, precision, batch_size):
   """(mode, group or None, lds_budget or None) of what `suite.load` builds for
   this batch size; mode REFUSED if `build_model` raises ValueError."""
-  calls = []
-  refused = False
-  with recording(calls):
+  with recording():
     try:
       suite.load(domain, first_task(domain), environment_kwargs={
           'batch_size': batch_size, 'precision': precision})
-    except _Recorded:
-      pass
+    except _Recorded as recorded:
+      spec = recorded.args[0]
     except ValueError:
-      refused = True
+      return REFUSED, None, None
     else:
       raise AssertionError('suite.load(%r) built nothing' % domain)
-  assert len(calls) == 1, calls
-  _, mode, group, lds_budget = calls[0]
-  if refused:
-    return REFUSED, None, None
-  if mode == 'coop':
-    return mode, group, None
-  return mode, None, lds_budget
+  assert spec.precision == precision
+  if spec.mode == 'coop':
+    return spec.mode, spec.group, None
+  return spec.mode, None, spec.lds_budget
 
 
 def enumerate_selections():

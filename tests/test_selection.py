@@ -29,9 +29,9 @@ def test_shipped_list_equals_the_policy():
 
 
 def test_the_recorder_leaves_the_product_as_it_was():
-  real_build, real_key = build.build_model, build.model_key
+  real = build.realise
   sm.select('cheetah', 'f32', 8192)
-  assert build.build_model is real_build and build.model_key is real_key
+  assert build.realise is real
 
 
 def test_humanoid_mixed_is_refused_by_name():
