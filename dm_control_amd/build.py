@@ -111,7 +111,7 @@ _ROLLED_FLAGS = ('-fno-unroll-loops',)
 
 
 def model_key(model, task, precision, ncon_max=None, extra_flags=(),
-              unroll=True):
+              unroll=True, per_env=()):
   src = os.path.join(_CSRC, 'dmc_kernels.hip')
   h = hashlib.sha1()
   h.update(model.content_hash().encode())
@@ -120,6 +120,8 @@ def model_key(model, task, precision, ncon_max=None, extra_flags=(),
       os.environ.get('DMC_PRAGMA_UNROLL_THRESHOLD', ''), int(unroll is True),
       ' '.join(_FP32_FLAGS),
       '' if unroll is True else ('semi' if unroll == 'semi' else ' '.join(_ROLLED_FLAGS)))).encode())
+  if per_env:       # (nothing added for (): the key of a build without per-env fields)
+    h.update(('/per_env=' + ','.join(per_env)).encode())
   for path in (src, os.path.join(_CSRC, 'dmc_coop.hip'),
                os.path.join(_CSRC, 'dmc_args.h'), codegen.__file__):
     with open(path, 'rb') as f:
@@ -223,12 +225,20 @@ _COOP = Tier(True, COOP_MAX_SGPR_SPILLS, _COOP_OVERBUDGET_MSG)
 # What `build_model` was asked (model .. lds_budget, as given) and what that
 # means: source file, compile precision, final -D flags, tiers in order.
 Spec = collections.namedtuple(
-    'Spec', 'model task ncon_max precision mode group lds_budget source real flags tiers')
+    'Spec', 'model task ncon_max precision mode group lds_budget source real flags tiers '
+            'per_env')
 
 
-def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group):
+def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
+         per_env=()):
   """Checks the arguments of `build_model` and resolves them into a `Spec`.
-  Pure: reads the environment, touches no file and starts no process."""
+  Pure: reads the environment, touches no file and starts no process.
+  `per_env`: model fields the kernels read per env (codegen.PER_ENV_FIELDS)."""
+  per_env = codegen.normalise_per_env(per_env)     # ValueError: unknown names
+  if per_env and mode == 'team':
+    raise codegen.UnsupportedModelError(
+        'per_env: per-env model fields are not implemented for mode="team" (big '
+        'scenes, soccer); build the team scene without per_env')
   if precision not in ('f32', 'f64', 'mixed'):
     raise ValueError('precision must be "f32", "f64" or "mixed"')
   if mode not in ('auto', 'unrolled', 'rolled', 'coop', 'team'):
@@ -269,7 +279,7 @@ def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group)
       tiers = (_UNROLLED,) + tiers if mode == 'auto' else (_UNROLLED,)
     source = 'dmc_kernels.hip'
   return Spec(model, task, ncon_max, precision, mode, group, lds_budget, source,
-              'f64' if precision == 'f64' else 'f32', flags, tiers)
+              'f64' if precision == 'f64' else 'f32', flags, tiers, per_env)
 
 
 def _flags(spec_, tier, remarks=False):
@@ -311,7 +321,7 @@ def _flags(spec_, tier, remarks=False):
 
 def _key(spec_, tier):
   return model_key(spec_.model, spec_.task, spec_.real, spec_.ncon_max,
-                   spec_.flags, tier.unroll)
+                   spec_.flags, tier.unroll, spec_.per_env)
 
 
 def _compile(spec_, tier, out, keep_temps):
@@ -325,7 +335,7 @@ def _compile(spec_, tier, out, keep_temps):
           tier.unroll, model.nv, model.nbody))
   header = os.path.join(os.path.dirname(out), 'model_%s.h' % _key(spec_, tier))
   text = codegen.generate_header(model, spec_.task, spec_.ncon_max,
-                                 unroll=tier.unroll is True)
+                                 unroll=tier.unroll is True, per_env=spec_.per_env)
   with open(header, 'w') as f:
     f.write(text)
   flags = _flags(spec_, tier, remarks=True)
@@ -367,15 +377,17 @@ def _compile_in_process(header_text, source, flags):
 
 
 def code_object_bytes(model, task=codegen.TASK_NONE, precision='f32',
-                      ncon_max=None, unroll=False, coop_group=None):
+                      ncon_max=None, unroll=False, coop_group=None, per_env=()):
   """gfx950 code object of `model` as bytes, built in-process (no hipcc, no
   files): the `mj_loadXML` route for a model that was not pre-built --
   `wrapper.HipModel.from_code(build.code_object_bytes(model))`.  The generic
   (rolled) build by default: it compiles in seconds for any model size."""
   mode = 'coop' if coop_group else 'unrolled' if unroll else 'rolled'
-  spec_ = spec(model, task, precision, ncon_max, (), mode, None, coop_group or 64)
+  spec_ = spec(model, task, precision, ncon_max, (), mode, None, coop_group or 64,
+               per_env)
   tier = spec_.tiers[-1]        # no spill counts on this route: strictly rolled
-  header = codegen.generate_header(model, task, ncon_max, unroll=tier.unroll is True)
+  header = codegen.generate_header(model, task, ncon_max, unroll=tier.unroll is True,
+                                   per_env=spec_.per_env)
   return _compile_in_process(header, spec_.source, _flags(spec_, tier))[0]
 
 
@@ -449,7 +461,7 @@ def realise(spec_, force=False, keep_temps=False):
 
 def build_model(model, task=codegen.TASK_NONE, precision='f32',
                 ncon_max=None, force=False, keep_temps=False, extra_flags=None,
-                mode='auto', lds_budget=None, group=64):
+                mode='auto', lds_budget=None, group=64, per_env=()):
   """Generates the constants header for `model` and compiles its kernels.
 
   mode: "unrolled" (static indexing, per-lane state in registers), "rolled"
@@ -460,6 +472,13 @@ def build_model(model, task=codegen.TASK_NONE, precision='f32',
   env together with its working set in LDS (csrc/dmc_coop.hip; the shape for
   nv ~ 20+ models and for small shards; 128 = 64 lanes + a helper wavefront).  Returns the path of the gfx950 code
   object; cached in-tree by content hash.
+
+  per_env: names of model fields (codegen.PER_ENV_FIELDS) that the kernels read
+  per env from the model-parameter block (DMC_FIELD_MODELPARAM) instead of the
+  compiled tables; () builds what a build without the argument builds.  A
+  varied build walks the same tiers: where its extra loads push it past the
+  spill budget of a tier the default build fits, its `.verdict` says "over" and
+  the next tier is taken.
   """
   return realise(spec(model, task, precision, ncon_max, extra_flags, mode,
-                      lds_budget, group), force, keep_temps)
+                      lds_budget, group, per_env), force, keep_temps)

@@ -15,6 +15,8 @@ Host-side logic restated here (independently of oracle/mjstep.c):
     k = 1/(dmax^2 tc^2 zeta^2), tc >= 2*dt (refsafe)
 """
 
+import collections
+
 import numpy as np
 
 from dm_control_amd.mjcf import model as mdl
@@ -299,8 +301,112 @@ def planar_in_xz(m):
   return True
 
 
-def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None):
-  """Returns the text of the constants header for model `m`."""
+# Model fields a build may read PER ENV from the model-parameter block
+# (DMC_FIELD_MODELPARAM, [row][nenv]) instead of the constexpr tables:
+# user-facing field -> the rows the kernels read for it.  Rows that follow from
+# others (mj_setConst: subtree masses, inverse weights, the solver's scale) are
+# part of the block whenever a field they depend on varies.
+PER_ENV_FIELDS = ('body_mass', 'body_inertia', 'dof_damping', 'dof_armature',
+                  'jnt_stiffness', 'actuator_gear', 'actuator_gainprm',
+                  'actuator_biasprm', 'geom_friction', 'gravity')
+_INERTIAL = ('body_mass', 'body_inertia', 'dof_armature')   # what M(qpos0) is made of
+MODEL_PARAM_ROWS = ('body_mass', 'body_subtreemass', 'body_inertia', 'dof_damping',
+                    'dof_armature', 'jnt_stiffness', 'actuator_gear',
+                    'actuator_gainprm', 'actuator_biasprm', 'gravity',
+                    'dof_invweight0', 'meaninertia',
+                    # per pair, by far the longest rows: last, so that the rest is a
+                    # prefix (what csrc/dmc_coop.hip stages in LDS)
+                    'pair_friction', 'pair_diag')
+
+
+def normalise_per_env(per_env):
+  """Tuple of user-facing field names in canonical order ('opt.gravity' = 'gravity')."""
+  if isinstance(per_env, str):
+    per_env = (per_env,)
+  names = set('gravity' if n == 'opt.gravity' else n for n in (per_env or ()))
+  unknown = sorted(names - set(PER_ENV_FIELDS))
+  if unknown:
+    raise ValueError('per_env: unknown field(s) %s; the fields that can vary per env '
+                     'are %s' % (', '.join(unknown), ', '.join(PER_ENV_FIELDS)))
+  return tuple(n for n in PER_ENV_FIELDS if n in names)
+
+
+def model_param_layout(m, per_env):
+  """Ordered {row name: (offset, extent)} of the model-parameter block of a
+  build with the fields `per_env` varied: the one definition that the kernels
+  (through the generated header) and the Python side share."""
+  per_env = normalise_per_env(per_env)
+  npair = len(collision_pairs(m)) if per_env else 0
+  inertial = any(n in per_env for n in _INERTIAL)
+  want = {
+      'body_mass': 'body_mass' in per_env, 'body_subtreemass': 'body_mass' in per_env,
+      'body_inertia': 'body_inertia' in per_env,
+      'dof_damping': 'dof_damping' in per_env, 'dof_armature': 'dof_armature' in per_env,
+      'jnt_stiffness': 'jnt_stiffness' in per_env,
+      'actuator_gear': 'actuator_gear' in per_env,
+      'actuator_gainprm': 'actuator_gainprm' in per_env,
+      'actuator_biasprm': 'actuator_biasprm' in per_env,
+      'pair_friction': 'geom_friction' in per_env,
+      'pair_diag': 'geom_friction' in per_env or inertial,
+      'gravity': 'gravity' in per_env,
+      'dof_invweight0': inertial, 'meaninertia': inertial}
+  extent = {
+      'body_mass': m.nbody, 'body_subtreemass': m.nbody, 'body_inertia': 3*m.nbody,
+      'dof_damping': m.nv, 'dof_armature': m.nv, 'jnt_stiffness': m.njnt,
+      'actuator_gear': m.nu, 'actuator_gainprm': 3*m.nu, 'actuator_biasprm': 3*m.nu,
+      'pair_friction': 5*npair, 'pair_diag': 6*npair, 'gravity': 3,
+      'dof_invweight0': m.nv, 'meaninertia': 1}
+  layout, offset = collections.OrderedDict(), 0
+  for name in MODEL_PARAM_ROWS:
+    if want[name] and extent[name] > 0:
+      layout[name] = (offset, int(extent[name]))
+      offset += int(extent[name])
+  return layout
+
+
+def pair_rows(m, pairs=None):
+  """(pair_friction [5 per pair], pair_diag [6 per pair]) of the static pair list:
+  the mixed friction coefficients and the solver's diagonal approximation."""
+  if pairs is None:
+    pairs = collision_pairs(m)
+  pair_fric, pair_diag = [], []
+  for g1, g2 in pairs:
+    fr = mix_pair(m, g1, g2)['friction']
+    b1, b2 = int(m.geom_bodyid[g1]), int(m.geom_bodyid[g2])
+    tran = float(m.body_invweight0[b1, 0] + m.body_invweight0[b2, 0])
+    rot = float(m.body_invweight0[b1, 1] + m.body_invweight0[b2, 1])
+    # diagApprox: [frictionless/normal, pyramid edge k=1..5]
+    diag = [tran] + [tran + fr[k]*fr[k]*(tran if k < 2 else rot)
+                     for k in range(5)]
+    pair_diag.extend(diag)
+    pair_fric.extend(fr)
+  return pair_fric, pair_diag
+
+
+def model_param_values(m, layout):
+  """The rows of `layout` for model `m`, flattened in block order (fp64)."""
+  out = np.zeros(sum(n for _, n in layout.values()))
+  fric = diag = None
+  for name, (o, n) in layout.items():
+    if name in ('pair_friction', 'pair_diag'):
+      if fric is None:
+        fric, diag = pair_rows(m)
+      v = fric if name == 'pair_friction' else diag
+    elif name == 'meaninertia':
+      v = [m.meaninertia]
+    elif name == 'gravity':
+      v = m.opt.gravity
+    else:
+      v = getattr(m, name)
+    out[o:o + n] = np.asarray(v, np.float64).ravel()
+  return out
+
+
+def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=()):
+  """Returns the text of the constants header for model `m`.  `per_env`: fields
+  the kernels read per env from the model-parameter block (model_param_layout);
+  empty: every field is a compile-time table."""
+  layout = model_param_layout(m, per_env)
   if m.opt.cone != mdl.CONE_PYRAMIDAL:
     raise UnsupportedModelError('only pyramidal cones are implemented')
   if m.opt.solver != mdl.SOLVER_NEWTON:
@@ -325,21 +431,13 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None):
     limit_b.append(b)
     limit_solimp.extend(_sanitise_solimp(m.jnt_solimp[j]))
 
-  pair_k, pair_b, pair_solimp, pair_diag, pair_fric = [], [], [], [], []
-  for (g1, g2), mx in zip(pairs, mixed):
+  pair_k, pair_b, pair_solimp = [], [], []
+  for mx in mixed:
     k, b = _kb(mx['solref'], mx['solimp'], dt, refsafe)
     pair_k.append(k)
     pair_b.append(b)
     pair_solimp.extend(_sanitise_solimp(mx['solimp']))
-    b1, b2 = int(m.geom_bodyid[g1]), int(m.geom_bodyid[g2])
-    tran = float(m.body_invweight0[b1, 0] + m.body_invweight0[b2, 0])
-    rot = float(m.body_invweight0[b1, 1] + m.body_invweight0[b2, 1])
-    fr = mx['friction']
-    # diagApprox: [frictionless/normal, pyramid edge k=1..5]
-    diag = [tran] + [tran + fr[k]*fr[k]*(tran if k < 2 else rot)
-                     for k in range(5)]
-    pair_diag.extend(diag)
-    pair_fric.extend(fr)
+  pair_fric, pair_diag = pair_rows(m, pairs)
 
   out = []
   w = out.append
@@ -361,6 +459,12 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None):
   unroll_pairs = unroll and len(pairs) <= max_unrolled_pairs
   w('#define DMC_UNROLL_PAIRS %s' % ('_Pragma("unroll")' if unroll_pairs else ''))
   w('#define DMC_PAIRS_UNROLLED %d' % (1 if unroll_pairs else 0))
+  # fields read per env: switch and row offset in the block (csrc/dmc_kernels.hip, "MP")
+  for name, (offset, _) in layout.items():
+    w('#define DMC_VARY_%s 1' % name.upper())
+    w('#define DMC_MP_%s %d' % (name.upper(), offset))
+  if layout:
+    w('#define DMC_NMODELPARAM %d' % sum(n for _, n in layout.values()))
   w('namespace dmc_model {')
 
   def ci(name, v):
@@ -675,6 +779,9 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None):
     width = {mdl.JNT_FREE: 6, mdl.JNT_BALL: 3}.get(int(m.jnt_type[j]), 1)
     for k in range(width):
       dof_jntid[int(m.jnt_dofadr[j]) + k] = j
+  if layout:
+    ci('NMODELPARAM', sum(n for _, n in layout.values()))
+    tr('model_param_default', model_param_values(m, layout))
   ci('NLEVEL', nlevel)
   ti('level_adr', level_adr)
   ti('level_body', order)

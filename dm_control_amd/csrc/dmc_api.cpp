@@ -126,6 +126,7 @@ void fill_args(dmc_batch* b, DmcArgs& a) {
   a.reward = b->field[DMC_FIELD_REWARD];
   a.episode_return = b->field[DMC_FIELD_RETURN];
   a.taskdata = b->field[DMC_FIELD_TASKDATA];
+  a.modelparam = b->field[DMC_FIELD_MODELPARAM];
   a.sensordata = b->field[DMC_FIELD_SENSORDATA];
   a.xpos = b->aux_outputs ? b->field[DMC_FIELD_XPOS] : nullptr;
   a.xmat = b->aux_outputs ? b->field[DMC_FIELD_XMAT] : nullptr;
@@ -139,7 +140,7 @@ void fill_args(dmc_batch* b, DmcArgs& a) {
 
 extern "C" {
 
-int dmc_version(void) { return 100; }
+int dmc_version(void) { return 101; }   // 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -342,6 +343,7 @@ int load_model(const char* path, const void* image, int device_id, dmc_model** o
   i.lanes_per_env = raw[17] > i.envs_per_block ? raw[17]/i.envs_per_block : 1;
   i.env_major = raw[15] != 0;
   i.ntaskdata = raw[16];
+  i.nmodelparam = raw[18] > 0 ? raw[18] : 0;
   *out = m;
   return 0;
 }
@@ -389,6 +391,7 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   b->bytes[DMC_FIELD_STATS] = 3*n*sizeof(int);
   b->bytes[DMC_FIELD_RETURN] = n*rs;
   b->bytes[DMC_FIELD_TASKDATA] = atleast1(i.ntaskdata)*n*rs;
+  b->bytes[DMC_FIELD_MODELPARAM] = atleast1(i.nmodelparam)*n*rs;
   for (int f = 0; f < DMC_FIELD_COUNT; f++) {
     b->elem[f] = (f == DMC_FIELD_WARN || f == DMC_FIELD_STATS) ? sizeof(int) : rs;
     b->rows[f] = b->bytes[f]/(n*b->elem[f]);
@@ -415,7 +418,7 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
     return fail("dmc_batch_create: %s", hipGetErrorString(err));
   }
   *out = b;
-  {   // per-instance task data starts from the compiled model's values
+  {   // per-instance task data and model parameters start from the compiled model's values
     DmcArgs a;
     fill_args(b, a);
     a.flags = DMC_FLAG_RESET_ONLY | DMC_FLAG_TASKDATA_DEFAULT;
@@ -496,11 +499,12 @@ int dmc_batch_set_state(dmc_batch* b, const void* qpos, const void* qvel,
 
 int dmc_batch_write(dmc_batch* b, int field, const void* src, size_t bytes) {
   if (!b || !src) return fail("dmc_batch_write: null argument");
-  // the integration state, the per-instance task data and what a checkpoint
+  // the integration state, the per-instance task data and model parameters, and what a checkpoint
   // must restore besides (last applied control, episode return, warning mask)
   if (field != DMC_FIELD_QPOS && field != DMC_FIELD_QVEL &&
       field != DMC_FIELD_WARMSTART && field != DMC_FIELD_TIME &&
-      field != DMC_FIELD_TASKDATA && field != DMC_FIELD_CTRL &&
+      field != DMC_FIELD_TASKDATA && field != DMC_FIELD_MODELPARAM &&
+      field != DMC_FIELD_CTRL &&
       field != DMC_FIELD_RETURN && field != DMC_FIELD_WARN)
     return fail("dmc_batch_write: field %d is not writable", field);
   if (bytes != b->bytes[field])
@@ -632,7 +636,9 @@ int dmc_batch_copy_state(dmc_batch* dst, const dmc_batch* src) {
   if (!dst || !src) return fail("null batch");
   if (dst->nenv != src->nenv || dst->model->info.nq != src->model->info.nq ||
       dst->model->info.real_size != src->model->info.real_size ||
-      dst->model->info.env_major != src->model->info.env_major)
+      dst->model->info.env_major != src->model->info.env_major ||
+      dst->model->info.ntaskdata != src->model->info.ntaskdata ||
+      dst->model->info.nmodelparam != src->model->info.nmodelparam)
     return fail("dmc_batch_copy_state: incompatible batches");
   HIP_TRY(hipSetDevice(dst->model->device));
   HIP_TRY(hipStreamSynchronize(src->stream));

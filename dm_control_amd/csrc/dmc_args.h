@@ -30,6 +30,7 @@ struct DmcArgs {
   DMC_REALPTR ws;          // workspace, ws_per_env reals per env, [idx][nenv]
   DMC_REALPTR taskdata;    // [NTASKDATA][nenv] per-instance task parameters
   double task_param_r[4];
+  DMC_REALPTR modelparam;  // [NMODELPARAM][nenv] model fields read per env (builds with per-env fields)
 };
 // dmc_step flags
 #define DMC_FLAG_CTRL 1          // ctrl pointer valid (else reuse ctrl_store)
@@ -37,5 +38,5 @@ struct DmcArgs {
 #define DMC_FLAG_COUNT_CONTACTS 4
 #define DMC_FLAG_ONLY_COLLIDING 8
 #define DMC_FLAG_RESET_ONLY 16     // dmc_init_episode: mj_resetData only
-#define DMC_FLAG_TASKDATA_DEFAULT 32  // dmc_init_episode: task data <- model values
+#define DMC_FLAG_TASKDATA_DEFAULT 32  // dmc_init_episode: task data and model parameters <- model values
 #define DMC_FLAG_STALE_FIRST 64    // dmc_step: first substep takes its acceleration from the reset state

@@ -73,11 +73,18 @@ constexpr bool RK4 = INTEGRATOR != 0;
 constexpr bool DUO = DMC_COOP_DUO != 0 && G == 64 && !RK4;
 constexpr int NTHREADS = DUO ? 128 : 64;
 constexpr bool coop_damped() {
-  bool d = false;
+  bool d = DMC_VARY_DOF_DAMPING != 0;      // (varied: any value, so always the damped form)
   for (int i = 0; i < NV; i++) d = d || dof_damping[i] > 0;
   return d;
 }
 
+// Model parameters read per env (dmc_kernels.hip, "MP"): the env's rows are staged
+// in its LDS record, next to the task data, except the two per-pair rows -- the
+// last of the block, and most of it (humanoid: 1771 of 2110 words) -- which the
+// row builder reads from the env's (contiguous, env-major) block in HBM, once
+// per contact.
+constexpr int MP_LDS = DMC_VARY_PAIR_FRICTION ? DMC_MP_PAIR_FRICTION
+                       : (DMC_VARY_PAIR_DIAG ? DMC_MP_PAIR_DIAG : DMC_NMODELPARAM);
 // word offsets of the per-env LDS region
 namespace off {
 constexpr int QPOS = 0;
@@ -126,7 +133,8 @@ constexpr int SLV = ROWS + NEFC_MAX*CRW;
 constexpr int TOUCH = SLV + NBODY*3;     // touch sensor readings
 constexpr int XCH = TOUCH + (NTOUCH > 0 ? NTOUCH : 1);      // nefc, ncon, warn from the row-building wave
 constexpr int TASKD = XCH + 4;          // (+ the velocity-stage flag) per-instance task parameters
-constexpr int OBSV = TASKD + NTDX;
+constexpr int MP = TASKD + NTDX;         // model parameters of this env (MP_LDS words)
+constexpr int OBSV = MP + MP_LDS;
 constexpr int Q0 = OBSV + NOBSX;        // RK4 stage storage
 constexpr int V0 = Q0 + (RK4 ? NQX : 0);
 constexpr int FV = V0 + (RK4 ? NVX : 0);
@@ -357,6 +365,11 @@ struct Coop {
   unsigned warn;
   int ncon, nefc, iters;
   int epoch;       // forward() calls so far (DUO: value of the velocity-stage flag)
+  const real* mpg; // this env's model-parameter block in HBM (builds with per-env fields)
+  template <int OFF> __device__ __forceinline__ real mp_at(int i) const {
+    if constexpr (OFF < MP_LDS) return S[off::MP + OFF + i];
+    else return mpg[OFF + i];
+  }
 #ifdef DMC_COOP_PROFILE
   long long tprof[PH_N], tlast;
 #endif
@@ -672,11 +685,11 @@ struct Coop {
       for (int jj = 0; jj < NBODY; jj++) {
         const bool in = jj < n;
         const int j = in ? i + jj : i;
-        const real mass = in ? R(body_mass[j]) : R(0);
+        const real mass = in ? MP_body_mass(*this, j) : R(0);
         acc += mass*S[off::XIPOS + 3*j + k];
       }
-      if (body_subtreemass[i] < 1e-15) acc = S[off::XIPOS + idx];
-      else acc *= R(1)/R(body_subtreemass[i]);
+      if (MP_body_subtreemass(*this, i) < 1e-15) acc = S[off::XIPOS + idx];
+      else acc *= R(1)/MP_body_subtreemass(*this, i);
       S[off::SUBCOM + idx] = acc;
     }
     gsync();
@@ -686,9 +699,9 @@ struct Coop {
       const real* com = S + off::SUBCOM + 3*body_rootid[i];
       const real* mat = S + off::XIMAT + 9*i;
       real dif[3], t[9], m[9];
-      const real mass = R(body_mass[i]);
-      const real in0 = R(body_inertia[3*i]), in1 = R(body_inertia[3*i + 1]),
-                 in2 = R(body_inertia[3*i + 2]);
+      const real mass = MP_body_mass(*this, i);
+      const real in0 = MP_body_inertia(*this, 3*i), in1 = MP_body_inertia(*this, 3*i + 1),
+                 in2 = MP_body_inertia(*this, 3*i + 2);
       for (int k = 0; k < 9; k++) m[k] = mat[k];
       for (int k = 0; k < 3; k++) dif[k] = S[off::XIPOS + 3*i + k] - com[k];
       for (int a = 0; a < 3; a++)
@@ -766,7 +779,7 @@ struct Coop {
       const int row = opaque(i*MAXCHAIN);
       _Pragma("unroll")
       for (int a = 0; a < MAXCHAIN; a++) anc[a] = dof_anc[row + a];
-      const real diag = dot6(cd, buf) + R(dof_armature[i]);
+      const real diag = dot6(cd, buf) + MP_dof_armature(*this, i);
       _Pragma("unroll")
       for (int a = 0; a < MAXCHAIN; a++) {
         // branch-free: the slots past the end of the chain rewrite the diagonal
@@ -822,7 +835,7 @@ struct Coop {
     for (int i = l; i < NBODY; i += G) {
       real cvel[6] = {0, 0, 0, 0, 0, 0}, cacc[6] = {0, 0, 0, 0, 0, 0};
       if (!(DISABLEFLAGS & DSBL_GRAVITY))
-        for (int k = 0; k < 3; k++) cacc[3 + k] = -R(gravity[k]);
+        for (int k = 0; k < 3; k++) cacc[3 + k] = -MP_gravity(*this, k);
       const int last = body_lastdof[i];
       const int lastx = last < 0 ? 0 : last;
       const int na = last < 0 ? -1 : dof_anc_len[lastx];
@@ -886,11 +899,11 @@ struct Coop {
       real fs = -dot6(cd, f);
       if (!(DISABLEFLAGS & DSBL_PASSIVE)) {
         const int j = dof_jntid[i], jt = jnt_type[j];
-        if (jnt_stiffness[j] != 0 && (jt == JNT_SLIDE || jt == JNT_HINGE)) {
+        if ((DMC_VARY_JNT_STIFFNESS || jnt_stiffness[j] != 0) && (jt == JNT_SLIDE || jt == JNT_HINGE)) {
           const int qa = jnt_qposadr[j];
-          fs -= R(jnt_stiffness[j])*(S[off::QPOS + qa] - R(qpos_spring[qa]));
+          fs -= MP_jnt_stiffness(*this, j)*(S[off::QPOS + qa] - R(qpos_spring[qa]));
         }
-        fs -= R(dof_damping[i])*S[off::QVEL + i];
+        fs -= MP_dof_damping(*this, i)*S[off::QVEL + i];
       }
       if (actuation && !(DISABLEFLAGS & DSBL_ACTUATION)) {
         const EnvView V = {S + off::QPOS, S + off::QVEL, S + off::CTRL, S + off::XPOS,
@@ -908,11 +921,11 @@ struct Coop {
             const int w = act_wrap_adr[u] + k;
             if (act_wrap_dof[w] == i) { moment += wrap_coef(V, w); mine = true; }
           }
-          const real gear = R(actuator_gear[u]);
+          const real gear = MP_actuator_gear(*this, u);
           real c = S[off::CTRL + u];
           if (actuator_ctrllimited[u] && !(DISABLEFLAGS & DSBL_CLAMPCTRL))
             c = clampr(c, R(actuator_ctrlrange[2*u]), R(actuator_ctrlrange[2*u + 1]));
-          real force = R(actuator_gainprm[3*u])*c;
+          real force = MP_actuator_gainprm(*this, 3*u)*c;
           if (actuator_biastype[u] == 1) {
             real length = 0, velocity = 0;
             _Pragma("unroll")
@@ -922,8 +935,8 @@ struct Coop {
               length += coef*S[off::QPOS + act_wrap_qadr[w]];
               velocity += coef*S[off::QVEL + act_wrap_dof[w]];
             }
-            force += R(actuator_biasprm[3*u]) + R(actuator_biasprm[3*u + 1])*gear*length +
-                     R(actuator_biasprm[3*u + 2])*gear*velocity;
+            force += MP_actuator_biasprm(*this, 3*u) + MP_actuator_biasprm(*this, 3*u + 1)*gear*length +
+                     MP_actuator_biasprm(*this, 3*u + 2)*gear*velocity;
           }
           if (actuator_forcelimited[u])
             force = clampr(force, R(actuator_forcerange[2*u]), R(actuator_forcerange[2*u + 1]));
@@ -960,7 +973,7 @@ struct Coop {
       for (int k = 0; k < 3; k++) { dif[k] = S[off::XIPOS + 3*i + k] - com[k]; w[k] = S[off::CVEL + 6*i + k]; }
       cross3(t, w, dif);
       for (int k = 0; k < 3; k++)
-        S[off::CFRC + 3*i + k] = R(body_mass[i])*(S[off::CVEL + 6*i + 3 + k] + t[k]);
+        S[off::CFRC + 3*i + k] = MP_body_mass(*this, i)*(S[off::CVEL + 6*i + 3 + k] + t[k]);
     }
     gsync();
     for (int i = l; i < NBODY; i += G) {
@@ -968,7 +981,7 @@ struct Coop {
       const int n = body_subtree_n[i];
       for (int j = i; j < i + n; j++)
         for (int k = 0; k < 3; k++) acc[k] += S[off::CFRC + 3*j + k];
-      const real inv = R(1.0/(body_subtreemass[i] < 1e-15 ? 1e-15 : body_subtreemass[i]));
+      const real inv = MP_inv_subtreemass(*this, i, 1e-15, 1e-15);
       for (int k = 0; k < 3; k++) S[off::SLV + 3*i + k] = acc[k]*inv;
     }
     gsync();
@@ -1011,7 +1024,7 @@ struct Coop {
         const real pm = dist[side] - margin;
         const real imp = impedance(limit_solimp + 5*li, pm);
         row_meta(r, pm, R(limit_K[li]), R(limit_B[li]), imp,
-                 (1 - imp)*R(dof_invweight0[dof])/imp);
+                 (1 - imp)*MP_dof_invweight0(*this, dof)/imp);
         r++;
       }
       nefc += total;
@@ -1137,10 +1150,10 @@ struct Coop {
         const real pm = dist - R(pair_includemargin[p]);
         const real imp = impedance(pair_solimp + 5*p, pm);
         const real K = R(pair_K[p]), B = R(pair_B[p]);
-        const real mu0 = R(pair_friction[5*p]);
-        real R0 = (1 - imp)*R(pair_diag[6*p + 1])/imp;
+        const real mu0 = MP_pair_friction(*this, 5*p);
+        real R0 = (1 - imp)*MP_pair_diag(*this, 6*p + 1)/imp;
         if (R0 < DMC_MINVAL) R0 = DMC_MINVAL;
-        const real Rrow = dim == 1 ? (1 - imp)*R(pair_diag[6*p])/imp : 2*mu0*mu0*R0;
+        const real Rrow = dim == 1 ? (1 - imp)*MP_pair_diag(*this, 6*p)/imp : 2*mu0*mu0*R0;
         for (int r = r0; r < r0 + nrow && r < NEFC_MAX; r++) row_meta(r, pm, K, B, imp, Rrow);
       }
       real cd[6], jb[3], jt[3];
@@ -1161,7 +1174,7 @@ struct Coop {
         if (r0 < NEFC_MAX) col[r0*CRW] = jb[0];
       } else {
         for (int k = 1; k < dim; k++) {
-          const real mu = R(pair_friction[5*p + k - 1]);
+          const real mu = MP_pair_friction(*this, 5*p + k - 1);
           const real t = k < 3 ? jb[k] : jt[k - 3];
           const int r = r0 + 2*(k - 1);
           if (r < NEFC_MAX) col[r*CRW] = jb[0] + mu*t;
@@ -1215,7 +1228,7 @@ struct Coop {
   // alpha = 1, the exact Newton step, so the usual iteration needs no further
   // line-search pass.
   __device__ __forceinline__ void solve_newton(real tol) {
-    const real scale = R(1.0/(meaninertia*(NV > 1 ? NV : 1)));
+    const real scale = mp_solver_scale(*this);
     for (int i = l; i < NV; i += G) S[off::MA + i] = mrow_dot(i, off::QACC);
     gsync();
     real improvement = 0;
@@ -1616,7 +1629,7 @@ struct Coop {
       const int i = l + t*G;
       _Pragma("unroll")
       for (int k = 0; k < NV; k++)
-        if (i == k) A.a[t][k] += h*R(dof_damping[k]);
+        if (i == k) A.a[t][k] += h*MP_dof_damping(*this, k);
     }
     rows_chol(A, panel);
   }
@@ -1746,6 +1759,7 @@ struct Coop {
     warn = 0; ncon = 0; nefc = 0; iters = 0; epoch = 0;
     if (l < (NTOUCH > 0 ? NTOUCH : 1)) S[off::TOUCH + l] = 0;
     for (int i = l; i < NTASKDATA; i += G) S[off::TASKD + i] = a.taskdata[sidx(i, e, n, NTDX)];
+    for (int i = l; i < MP_LDS; i += G) S[off::MP + i] = mpg[i];
   }
   __device__ __forceinline__ void store(const DmcArgs& a, int e) {
     const long long n = a.nenv;
@@ -1825,6 +1839,7 @@ dmc_step(DmcArgs a) {
   const int l = C.l;
   real* S = C.S;
   const long long n = a.nenv;
+  C.mpg = DMC_NMODELPARAM > 0 ? a.modelparam + (long long)e*DMC_NMODELPARAM : nullptr;
 #ifdef DMC_COOP_PROFILE
   for (int k = 0; k < PH_N; k++) C.tprof[k] = 0;
   C.tlast = wall_clock64();
@@ -1893,6 +1908,7 @@ dmc_observe(DmcArgs a) {
   const int l = C.l;
   real* S = C.S;
   const long long n = a.nenv;
+  C.mpg = DMC_NMODELPARAM > 0 ? a.modelparam + (long long)e*DMC_NMODELPARAM : nullptr;
 #ifdef DMC_COOP_PROFILE
   for (int k = 0; k < PH_N; k++) C.tprof[k] = 0;
   C.tlast = 0;
@@ -1930,4 +1946,4 @@ extern "C" __device__ const int dmc_info[20] = {
     1 /*workspace reals per env: none, everything is in LDS*/, TASK, NCON_MAX, NEFC_MAX,
     INTEGRATOR, NPAIR, EPB /*envs per 64-lane workgroup*/,
     DMC_ENV_MAJOR /*state fields are [env][k]*/, NTASKDATA, NTHREADS /*threads per workgroup*/,
-    0, 0};
+    DMC_NMODELPARAM /*rows of the model-parameter block*/, 0};

@@ -71,6 +71,115 @@ typedef float real;
 
 using namespace dmc_model;
 
+// ---------------------------------------------------------------------------
+// Model parameters read PER ENV (domain randomisation).  A build names the
+// fields that vary (codegen.generate_header, per_env): for those the generated
+// header defines DMC_VARY_<ROW> and the row's offset DMC_MP_<ROW> in the
+// model-parameter block (DmcArgs::modelparam, [row][nenv] like the task data),
+// and MP_<row>(E, i) reads this env's value there; for every other field it
+// reads the constexpr table, as a build without per-env fields does everywhere.
+// The choice is made here, at compile time, once per field.
+// Team mode (DMC_TEAM) does not take per-env fields (static_assert below), so the
+// functions only it reaches keep reading the tables directly: team_factor,
+// crb_rows_team, passive_forces / actuator_forces (called from forward_team),
+// rows_of_contact_team, solve_newton_team, the seg_* recursions, limit_rows_team
+// and the TEAMED branch of physics_step.
+// ---------------------------------------------------------------------------
+#ifndef DMC_NMODELPARAM
+#define DMC_NMODELPARAM 0
+#endif
+#ifndef DMC_VARY_BODY_MASS
+#define DMC_VARY_BODY_MASS 0
+#define DMC_MP_BODY_MASS 0
+#endif
+#ifndef DMC_VARY_BODY_SUBTREEMASS
+#define DMC_VARY_BODY_SUBTREEMASS 0
+#define DMC_MP_BODY_SUBTREEMASS 0
+#endif
+#ifndef DMC_VARY_BODY_INERTIA
+#define DMC_VARY_BODY_INERTIA 0
+#define DMC_MP_BODY_INERTIA 0
+#endif
+#ifndef DMC_VARY_DOF_DAMPING
+#define DMC_VARY_DOF_DAMPING 0
+#define DMC_MP_DOF_DAMPING 0
+#endif
+#ifndef DMC_VARY_DOF_ARMATURE
+#define DMC_VARY_DOF_ARMATURE 0
+#define DMC_MP_DOF_ARMATURE 0
+#endif
+#ifndef DMC_VARY_JNT_STIFFNESS
+#define DMC_VARY_JNT_STIFFNESS 0
+#define DMC_MP_JNT_STIFFNESS 0
+#endif
+#ifndef DMC_VARY_ACTUATOR_GEAR
+#define DMC_VARY_ACTUATOR_GEAR 0
+#define DMC_MP_ACTUATOR_GEAR 0
+#endif
+#ifndef DMC_VARY_ACTUATOR_GAINPRM
+#define DMC_VARY_ACTUATOR_GAINPRM 0
+#define DMC_MP_ACTUATOR_GAINPRM 0
+#endif
+#ifndef DMC_VARY_ACTUATOR_BIASPRM
+#define DMC_VARY_ACTUATOR_BIASPRM 0
+#define DMC_MP_ACTUATOR_BIASPRM 0
+#endif
+#ifndef DMC_VARY_GRAVITY
+#define DMC_VARY_GRAVITY 0
+#define DMC_MP_GRAVITY 0
+#endif
+#ifndef DMC_VARY_DOF_INVWEIGHT0
+#define DMC_VARY_DOF_INVWEIGHT0 0
+#define DMC_MP_DOF_INVWEIGHT0 0
+#endif
+#ifndef DMC_VARY_MEANINERTIA
+#define DMC_VARY_MEANINERTIA 0
+#define DMC_MP_MEANINERTIA 0
+#endif
+#ifndef DMC_VARY_PAIR_FRICTION
+#define DMC_VARY_PAIR_FRICTION 0
+#define DMC_MP_PAIR_FRICTION 0
+#endif
+#ifndef DMC_VARY_PAIR_DIAG
+#define DMC_VARY_PAIR_DIAG 0
+#define DMC_MP_PAIR_DIAG 0
+#endif
+template <bool VARY, int OFF, class EnvT, class T>
+static __device__ __forceinline__ real mp_read(const EnvT& E, const T& table, int i) {
+  if constexpr (VARY) return E.template mp_at<OFF>(i);
+  else return (real)table[i];
+}
+#define MP_body_mass(E, i) mp_read<DMC_VARY_BODY_MASS != 0, DMC_MP_BODY_MASS>(E, body_mass, i)
+#define MP_body_subtreemass(E, i) mp_read<DMC_VARY_BODY_SUBTREEMASS != 0, DMC_MP_BODY_SUBTREEMASS>(E, body_subtreemass, i)
+#define MP_body_inertia(E, i) mp_read<DMC_VARY_BODY_INERTIA != 0, DMC_MP_BODY_INERTIA>(E, body_inertia, i)
+#define MP_dof_damping(E, i) mp_read<DMC_VARY_DOF_DAMPING != 0, DMC_MP_DOF_DAMPING>(E, dof_damping, i)
+#define MP_dof_armature(E, i) mp_read<DMC_VARY_DOF_ARMATURE != 0, DMC_MP_DOF_ARMATURE>(E, dof_armature, i)
+#define MP_jnt_stiffness(E, i) mp_read<DMC_VARY_JNT_STIFFNESS != 0, DMC_MP_JNT_STIFFNESS>(E, jnt_stiffness, i)
+#define MP_actuator_gear(E, i) mp_read<DMC_VARY_ACTUATOR_GEAR != 0, DMC_MP_ACTUATOR_GEAR>(E, actuator_gear, i)
+#define MP_actuator_gainprm(E, i) mp_read<DMC_VARY_ACTUATOR_GAINPRM != 0, DMC_MP_ACTUATOR_GAINPRM>(E, actuator_gainprm, i)
+#define MP_actuator_biasprm(E, i) mp_read<DMC_VARY_ACTUATOR_BIASPRM != 0, DMC_MP_ACTUATOR_BIASPRM>(E, actuator_biasprm, i)
+#define MP_gravity(E, i) mp_read<DMC_VARY_GRAVITY != 0, DMC_MP_GRAVITY>(E, gravity, i)
+#define MP_dof_invweight0(E, i) mp_read<DMC_VARY_DOF_INVWEIGHT0 != 0, DMC_MP_DOF_INVWEIGHT0>(E, dof_invweight0, i)
+#define MP_pair_friction(E, i) mp_read<DMC_VARY_PAIR_FRICTION != 0, DMC_MP_PAIR_FRICTION>(E, pair_friction, i)
+#define MP_pair_diag(E, i) mp_read<DMC_VARY_PAIR_DIAG != 0, DMC_MP_PAIR_DIAG>(E, pair_diag, i)
+// 1/(meaninertia nv), the solver's cost scale
+template <class EnvT>
+static __device__ __forceinline__ real mp_solver_scale(const EnvT& E) {
+  if constexpr (DMC_VARY_MEANINERTIA != 0) return (real)1/(E.template mp_at<DMC_MP_MEANINERTIA>(0)*(real)(NV > 1 ? NV : 1));
+  else return (real)(1.0/(meaninertia*(NV > 1 ? NV : 1)));
+}
+// 1/max(subtree mass, floor); a table entry is divided at compile time
+template <class EnvT, class T>
+static __device__ __forceinline__ real mp_inv_subtreemass(const EnvT& E, const T& table, int i, double floor, double below) {
+  if constexpr (DMC_VARY_BODY_SUBTREEMASS != 0) {
+    const real v = E.template mp_at<DMC_MP_BODY_SUBTREEMASS>(i);
+    return (real)1/(v < (real)floor ? (real)below : v);
+  } else {
+    return (real)(1.0/(table[i] < floor ? below : table[i]));
+  }
+}
+#define MP_inv_subtreemass(E, i, floor, below) mp_inv_subtreemass(E, body_subtreemass, i, floor, below)
+
 // line-search evaluations per Newton iteration (experiments may lower it)
 #ifndef DMC_LS_MAXIT
 #define DMC_LS_MAXIT (DMC_F32_RULES ? 20 : 50)
@@ -100,6 +209,7 @@ static_assert(TEAM >= 2 && TEAM <= 64 && (TEAM & (TEAM - 1)) == 0, "team = power
 #else
 constexpr int TEAM = 1;
 #endif
+static_assert(TEAM == 1 || DMC_NMODELPARAM == 0, "team mode reads the compiled model's parameters only");
 constexpr bool TEAMED = TEAM > 1;
 // the lanes of a team in groups: a group per kinematic tree at a time (its first
 // lane runs the tree's recursions).  Group g = the lanes g, g + NGROUPS, ...: the
@@ -227,6 +337,7 @@ constexpr int NVX = NV > 0 ? NV : 1;
 constexpr int NUX = NU > 0 ? NU : 1;
 constexpr int NQX = NQ > 0 ? NQ : 1;
 constexpr int NTDX = NTASKDATA > 0 ? NTASKDATA : 1;
+constexpr int NMPX = DMC_NMODELPARAM > 0 ? DMC_NMODELPARAM : 1;
 constexpr real MAXVAL = R(1e10);
 
 enum { JNT_FREE = 0, JNT_BALL = 1, JNT_SLIDE = 2, JNT_HINGE = 3 };
@@ -622,6 +733,12 @@ struct Env {
   real subtree_linvel[NBODY*3];
   real touch[NTOUCH > 0 ? NTOUCH : 1];   // touch sensor readings (mj_sensorAcc)
   real taskdata[NTDX];                   // per-instance task parameters
+#if DMC_NMODELPARAM > 0
+  // this env's column of the model-parameter block: read where used (a wave's
+  // load of one row is coalesced; the block stays in L2 across substeps)
+  const real* mp; long long mpn;
+  template <int OFF> __device__ __forceinline__ real mp_at(int i) const { return mp[(OFF + i)*mpn]; }
+#endif
 #if defined(DMC_SOLVER_PROFILE) || defined(DMC_STEP_PROFILE)
   real prof[8];
 #endif
@@ -1572,7 +1689,7 @@ DEV void com_pos(Env& E) {
   for (int i = BODY_LO0(E); i < BODY_HI(E); i++)
     DMC_UNROLL
     for (int k = 0; k < 3; k++)
-      E.subtree_com[3*i + k] = R(body_mass[i])*E.xipos[3*i + k];
+      E.subtree_com[3*i + k] = MP_body_mass(E, i)*E.xipos[3*i + k];
   DMC_UNROLL
   for (int i = BODY_HI(E) - 1; i >= BODY_LO(E); i--) {
     if (TEAMED && body_parentid[i] == 0) continue;    // (the world's entry is shared and unused)
@@ -1582,11 +1699,11 @@ DEV void com_pos(Env& E) {
   }
   DMC_UNROLL
   for (int i = BODY_LO0(E); i < BODY_HI(E); i++) {
-    if (body_subtreemass[i] < 1e-15) {
+    if (MP_body_subtreemass(E, i) < 1e-15) {
       DMC_UNROLL
       for (int k = 0; k < 3; k++) E.subtree_com[3*i + k] = E.xipos[3*i + k];
     } else {
-      real inv = R(1.0/(body_subtreemass[i] < 1e-15 ? 1.0 : body_subtreemass[i]));
+      real inv = MP_inv_subtreemass(E, i, 1e-15, 1.0);
       DMC_UNROLL
       for (int k = 0; k < 3; k++) E.subtree_com[3*i + k] *= inv;
     }
@@ -1610,9 +1727,9 @@ DEV void com_pos_b(Env& E) {
     }
     const real* mat = MAT_IN_WS ? mat_ : E.ximat + 9*i;
     real dif[3], t[9];
-    const real mass = R(body_mass[i]);
-    const real in0 = R(body_inertia[3*i]), in1 = R(body_inertia[3*i + 1]),
-               in2 = R(body_inertia[3*i + 2]);
+    const real mass = MP_body_mass(E, i);
+    const real in0 = MP_body_inertia(E, 3*i), in1 = MP_body_inertia(E, 3*i + 1),
+               in2 = MP_body_inertia(E, 3*i + 2);
     DMC_UNROLL
     for (int k = 0; k < 3; k++) dif[k] = E.xipos[3*i + k] - com[k];
     DMC_UNROLL
@@ -1724,7 +1841,7 @@ DEV void crb_factor(Env& E, const Work& W) {
   for (int i = 0; i < NV; i++) {
     real buf[6];
     mul_inert_vec(buf, crb + 10*dof_bodyid[i], E.cdof + 6*i);
-    M.set(tri(i, i), dot6(E.cdof + 6*i, buf) + R(dof_armature[i]));
+    M.set(tri(i, i), dot6(E.cdof + 6*i, buf) + MP_dof_armature(E, i));
     DMC_UNROLL
     for (int a = 0; a < MAXCHAIN; a++)
       if (a < dof_anc_len[i]) {
@@ -1854,7 +1971,7 @@ DEV void smooth_forces(Env& E, const Work& W, bool actuation) {
   for (int k = 0; k < 6; k++) { cacc[k] = 0; cfrc[k] = 0; }
   if (!(DISABLEFLAGS & DSBL_GRAVITY))
     DMC_UNROLL
-    for (int k = 0; k < 3; k++) cacc[3 + k] = -R(gravity[k]);
+    for (int k = 0; k < 3; k++) cacc[3 + k] = -MP_gravity(E, k);
   DMC_UNROLL
   for (int i = BODY_LO(E); i < BODY_HI(E); i++) {
     real tmp[6], tmp1[6];
@@ -1887,26 +2004,26 @@ DEV void smooth_forces(Env& E, const Work& W, bool actuation) {
   if (!(DISABLEFLAGS & DSBL_PASSIVE)) {
     DMC_UNROLL
     for (int j = JNT_LO(E); j < JNT_HI(E); j++)
-      if (jnt_stiffness[j] != 0 &&
+      if ((DMC_VARY_JNT_STIFFNESS || jnt_stiffness[j] != 0) &&
           (jnt_type[j] == JNT_SLIDE || jnt_type[j] == JNT_HINGE)) {
         const int qa = jnt_qposadr[j];
         E.qfrc_smooth[jnt_dofadr[j]] -=
-            R(jnt_stiffness[j])*(E.qpos[qa] - R(qpos_spring[qa]));
+            MP_jnt_stiffness(E, j)*(E.qpos[qa] - R(qpos_spring[qa]));
       }
     DMC_UNROLL
     for (int i = DOF_LO(E); i < DOF_HI(E); i++)
-      E.qfrc_smooth[i] -= R(dof_damping[i])*E.qvel[i];
+      E.qfrc_smooth[i] -= MP_dof_damping(E, i)*E.qvel[i];
   }
   if (actuation && !(DISABLEFLAGS & DSBL_ACTUATION)) {
     // transmission = list of (dof, coefficient): a joint, or the joints a fixed
     // tendon wraps; the point-mass task varies the coefficients per instance
     DMC_UNROLL
     for (int i = ACT_LO(E); i < ACT_HI(E); i++) {
-      const real gear = R(actuator_gear[i]);
+      const real gear = MP_actuator_gear(E, i);
       real c = E.ctrl[i];
       if (actuator_ctrllimited[i] && !(DISABLEFLAGS & DSBL_CLAMPCTRL))
         c = clampr(c, R(actuator_ctrlrange[2*i]), R(actuator_ctrlrange[2*i + 1]));
-      real force = R(actuator_gainprm[3*i])*c;
+      real force = MP_actuator_gainprm(E, 3*i)*c;
       if (actuator_biastype[i] == 1) {
         real length = 0, velocity = 0;
         DMC_UNROLL
@@ -1916,8 +2033,8 @@ DEV void smooth_forces(Env& E, const Work& W, bool actuation) {
           length += coef*E.qpos[act_wrap_qadr[w]];
           velocity += coef*E.qvel[act_wrap_dof[w]];
         }
-        force += R(actuator_biasprm[3*i]) + R(actuator_biasprm[3*i + 1])*gear*length +
-                 R(actuator_biasprm[3*i + 2])*gear*velocity;
+        force += MP_actuator_biasprm(E, 3*i) + MP_actuator_biasprm(E, 3*i + 1)*gear*length +
+                 MP_actuator_biasprm(E, 3*i + 2)*gear*velocity;
       }
       if (actuator_forcelimited[i])
         force = clampr(force, R(actuator_forcerange[2*i]), R(actuator_forcerange[2*i + 1]));
@@ -1944,7 +2061,7 @@ DEV void subtree_vel(Env& E) {
     cross3(t, E.cvel + 6*i, dif);
     DMC_UNROLL
     for (int k = 0; k < 3; k++)
-      E.subtree_linvel[3*i + k] = R(body_mass[i])*(E.cvel[6*i + 3 + k] + t[k]);
+      E.subtree_linvel[3*i + k] = MP_body_mass(E, i)*(E.cvel[6*i + 3 + k] + t[k]);
   }
   DMC_UNROLL
   for (int i = BODY_HI(E) - 1; i >= BODY_LO(E); i--)
@@ -1953,7 +2070,7 @@ DEV void subtree_vel(Env& E) {
       E.subtree_linvel[3*body_parentid[i] + k] += E.subtree_linvel[3*i + k];
   DMC_UNROLL
   for (int i = BODY_LO0(E); i < BODY_HI(E); i++) {
-    real inv = R(1.0/(body_subtreemass[i] < 1e-15 ? 1e-15 : body_subtreemass[i]));
+    real inv = MP_inv_subtreemass(E, i, 1e-15, 1e-15);
     DMC_UNROLL
     for (int k = 0; k < 3; k++) E.subtree_linvel[3*i + k] *= inv;
   }
@@ -2063,7 +2180,7 @@ DEV void limit_rows(Env& E, const Work& W) {
       if (dist < margin) {
         const real pm = dist - margin;
         const real imp = impedance(limit_solimp + 5*l, pm);
-        const real Rr = (1 - imp)*R(dof_invweight0[dof])/imp;
+        const real Rr = (1 - imp)*MP_dof_invweight0(E, dof)/imp;
         if (MAT_IN_WS) {      // the record of a one-dof row, written directly
           push_row_1(E, W, dof, -(real)side, pm, R(limit_K[l]), R(limit_B[l]), imp, Rr);
         } else {
@@ -2854,19 +2971,19 @@ DEV void rows_of_contact(Env& E, const Work& W, const Rec& rec) {
     }
   }
   if (dim == 1) {
-    const real Rr = (1 - imp)*pair_diag[6*p]/imp;
+    const real Rr = (1 - imp)*MP_pair_diag(E, 6*p)/imp;
     push_row(E, W, jb[0], pm, K, B, imp, Rr);
     return;
   }
   // pyramidal: every edge gets 2 mu0^2 R(first edge)
-  const real mu0 = pair_friction[5*p];
-  real R0 = (1 - imp)*pair_diag[6*p + 1]/imp;
+  const real mu0 = MP_pair_friction(E, 5*p);
+  real R0 = (1 - imp)*MP_pair_diag(E, 6*p + 1)/imp;
   if (R0 < DMC_MINVAL) R0 = DMC_MINVAL;
   const real Rpy = 2*mu0*mu0*R0;
   int merged = 0;
   DMC_UNROLL
   for (int k = 1; k < 3; k++) {
-    const real mu = pair_friction[5*p + k - 1];
+    const real mu = MP_pair_friction(E, 5*p + k - 1);
     real row[NVX];
     // A model that moves inside the x-z plane (codegen.planar_in_xz) has a zero
     // Jacobian along world y, so for a tangent that is exactly +-y the two
@@ -2888,7 +3005,7 @@ DEV void rows_of_contact(Env& E, const Work& W, const Rec& rec) {
     for (int k = 3; k < 6; k++) {
       if (k >= dim) continue;
       const real* dir = f + 3*(k - 3);
-      const real mu = pair_friction[5*p + k - 1];
+      const real mu = MP_pair_friction(E, 5*p + k - 1);
       real jt[NVX], row[NVX];
       DMC_UNROLL
       for (int j = 0; j < NV; j++) {
@@ -3091,7 +3208,7 @@ DEV void solve_newton(Env& E, const Work& W, real tol, bool start_smooth) {
   // the factor of M is dead once qacc_smooth has been solved: its registers
   // take the factor of the Hessian
   const LaneMat F = Mats::L(E, W);
-  const real scale = R(1.0/(meaninertia*(NV > 1 ? NV : 1)));
+  const real scale = mp_solver_scale(E);
   const int nefc = E.nefc;
   if (MAT_IN_WS) {
     // envelope of the Hessian: M's, widened for the dofs of every constraint row
@@ -4137,7 +4254,7 @@ DEV void physics_step(Env& E, const Work& W, real& time, real tol, bool stale = 
     DMC_UNROLL
     for (int i = 0; i < NV; i++) ba |= bad(E.qacc[i]);
     if (ba) { E.warn |= WARN_BADQACC; reset_state(E, time); return; }
-    bool damped = false;
+    bool damped = DMC_VARY_DOF_DAMPING != 0;      // (varied: any value, so always the damped form)
     DMC_UNROLL
     for (int i = 0; i < NV; i++) damped |= dof_damping[i] > 0;
     real qacc[NVX];
@@ -4153,7 +4270,7 @@ DEV void physics_step(Env& E, const Work& W, real& time, real tol, bool stale = 
       }
       DMC_UNROLL
       for (int i = 0; i < NV; i++) {
-        A.set(tri(i, i), A.get(tri(i, i)) + h*R(dof_damping[i]));
+        A.set(tri(i, i), A.get(tri(i, i)) + h*MP_dof_damping(E, i));
         qacc[i] = E.qfrc_smooth[i] + E.qfrc_constraint[i];
       }
       if (MAT_IN_WS) {
@@ -4527,6 +4644,9 @@ DEV void load_env(Env& E, const DmcArgs& a, int e, real& time) {
 #endif
   DMC_UNROLL
   for (int i = 0; i < NTASKDATA; i++) E.taskdata[i] = a.taskdata[sidx(i, e, n, NTDX)];
+#if DMC_NMODELPARAM > 0
+  E.mp = a.modelparam + e; E.mpn = n;
+#endif
 #if defined(DMC_SOLVER_PROFILE) || defined(DMC_STEP_PROFILE)
   for (int k = 0; k < 8; k++) E.prof[k] = 0;
 #endif
@@ -4841,6 +4961,10 @@ dmc_init_episode(DmcArgs a) {
     DMC_UNROLL
     for (int i = 0; i < NTASKDATA; i++)
       a.taskdata[sidx(i, e, n, NTDX)] = R(task_data_default[i]);
+#if DMC_NMODELPARAM > 0
+    for (int i = 0; i < DMC_NMODELPARAM; i++)     // (rolled: up to a few thousand rows)
+      a.modelparam[sidx(i, e, n, NMPX)] = R(model_param_default[i]);
+#endif
   }
   if (TASK == TASK_POINTMASS && !(a.flags & DMC_FLAG_RESET_ONLY)) {
     // point_mass.py:103-113: each control drives a random direction in the
@@ -4886,5 +5010,5 @@ extern "C" __device__ const int dmc_info[20] = {
                                 threads unless a team of lanes shares an env);
                                 the workspace is sized for the batch rounded up to this*/,
     DMC_ENV_MAJOR /*0: state fields are [k][env]*/, NTASKDATA,
-    LANES /*threads per workgroup*/, 0, 0};
+    LANES /*threads per workgroup*/, DMC_NMODELPARAM /*rows of the model-parameter block*/, 0};
 #endif

@@ -27,6 +27,7 @@ import numpy as np
 from dm_control_amd import _dm_env as dm_env
 from dm_control_amd import build
 from dm_control_amd import codegen
+from dm_control_amd import model_params
 from dm_control_amd import wrapper
 from dm_control_amd.mjcf import compiler
 from dm_control_amd.mjcf import model as mdl
@@ -323,13 +324,38 @@ class _NamedArray:
   def __setitem__(self, key, value):
     raise ValueError(
         'the compiled model is immutable: what a task varies per episode is '
-        'per-instance task data (DMC_FIELD_TASKDATA), see suite/reacher.py')
+        'per-instance task data (DMC_FIELD_TASKDATA), see suite/reacher.py.  '
+        'Fields named in the `per_env` argument of Physics can be written per env.')
 
   def __array__(self, dtype=None, copy=None):
     return self._a if dtype is None else self._a.astype(dtype)
 
   def __repr__(self):
     return repr(self._a)
+
+
+class _PerEnvArray(_NamedArray):
+  """`named.model.<field>` of a field the batch reads per env: reads show the
+  compiled model's values (as for every field), a write of a scalar or of one
+  value per env goes to `Physics.set_model_params`.  A value is "one per env"
+  only if it is 1-D of length B and the key selects a single entry; for
+  anything else (slices, several rows) it is broadcast over the envs like a
+  numpy assignment to every env's copy -- use `set_model_params` to give a
+  slice different values per env."""
+
+  def __init__(self, array, rows, physics, name):
+    _NamedArray.__init__(self, array, rows)
+    self._physics, self._name = physics, name
+
+  def __setitem__(self, key, value):
+    idx = (self._row(key[0]),) + tuple(key[1:]) if isinstance(key, tuple) else self._row(key)
+    current = self._physics.get_model_params(self._name)       # [B, ...]
+    value = np.asarray(value, np.float64)
+    target = current[(slice(None),) + (idx if isinstance(idx, tuple) else (idx,))]
+    if value.ndim == 1 and value.shape[0] == current.shape[0] and target.ndim == 1:
+      pass        # one value per env for a single entry
+    current[(slice(None),) + (idx if isinstance(idx, tuple) else (idx,))] = value
+    self._physics.set_model_params(**{self._name: current})
 
 
 class _NamedModel:
@@ -339,14 +365,17 @@ class _NamedModel:
             ('site_', 'site'), ('actuator_', 'actuator'), ('sensor_', 'sensor'),
             ('tendon_', 'tendon'))
 
-  def __init__(self, model):
+  def __init__(self, model, physics=None):
     self._m = model
+    self._physics = physics
 
   def __getattr__(self, name):
     value = getattr(self._m, name)
     for prefix, kind in self._KINDS:
       if name.startswith(prefix) and isinstance(value, np.ndarray):
         rows = {n: i for i, n in enumerate(self._m.names.get(kind, [])) if n}
+        if name in getattr(self._physics, 'per_env', ()):
+          return _PerEnvArray(value, rows, self._physics, name)
         return _NamedArray(value, rows)
     return value
 
@@ -355,7 +384,7 @@ class _Named:
 
   def __init__(self, physics, data):
     self.data = _NamedData(physics, data)
-    self.model = _NamedModel(physics.model)
+    self.model = _NamedModel(physics.model, physics)
 
 
 class Physics(_control.Physics):
@@ -380,8 +409,10 @@ class Physics(_control.Physics):
   _GROUP = 64                 # lanes per env of build mode "coop" (128: two wavefronts)
 
   def __init__(self, model, batch_size=None, device=0, precision='f32',
-               task=None, ncon_max=None, build_mode=None, group=None):
+               task=None, ncon_max=None, build_mode=None, group=None, per_env=()):
     self.model = model
+    self._params = model_params.ModelParams(
+        model, per_env, 1 if batch_size is None else int(batch_size))
     self._squeeze = batch_size is None
     self._batch_size = 1 if batch_size is None else int(batch_size)
     self._task_id = self._TASK if task is None else task
@@ -407,7 +438,8 @@ class Physics(_control.Physics):
           break
     path = build.build_model(
         model, self._task_id, precision, ncon_max, mode=self._build_mode,
-        lds_budget=build.lds_budget_for(self._batch_size), group=self._group)
+        lds_budget=build.lds_budget_for(self._batch_size), group=self._group,
+        per_env=self._params.per_env)
     self._code_object = path
     self._hip_model = wrapper.HipModel(path, device)
     self._batch = wrapper.HipBatch(self._hip_model, self._batch_size)
@@ -441,6 +473,35 @@ class Physics(_control.Physics):
   @property
   def dtype(self):
     return self._hip_model.dtype
+
+  # -- per-env model parameters (domain randomisation) ----------------------------
+  @property
+  def per_env(self):
+    """The model fields this batch reads per env (the `per_env` argument)."""
+    return self._params.per_env
+
+  def set_model_params(self, envs=None, set_const=True, **fields):
+    """Writes per-env values of fields named in `per_env`.
+
+    fields: `name=array`, [B', ...] with one entry per selected env or [...]
+    (broadcast): body_mass [nbody], body_inertia [nbody, 3], dof_damping /
+    dof_armature [nv], jnt_stiffness [njnt], actuator_gear [nu],
+    actuator_gainprm / actuator_biasprm [nu, 3], geom_friction [ngeom, 3],
+    gravity [3].  envs: index array or boolean mask (default: all).
+    set_const: recompute what `mj_setConst` would (subtree masses, inverse
+    weights, the contact rows' diagonal, the solver's scale), so that each env
+    equals the model the compiler would produce from its values; False writes
+    the raw rows only, as a bare array write does in the reference.  Raises
+    ValueError for a field that is not in `per_env`, and for envs whose mass
+    matrix would not be positive definite (nothing is written then).  The
+    values survive `reset()` and episode boundaries: they belong to the model."""
+    block = self._params.set(fields, envs, set_const)
+    self._batch.write(wrapper.FIELD_MODELPARAM, block)
+    self._dirty = True
+
+  def get_model_params(self, name):
+    """[B, ...] current values of a field (or of a derived row), fp64 as set."""
+    return self._params.get(name)
 
   @property
   def code_object(self):
@@ -623,8 +684,12 @@ class Physics(_control.Physics):
     Physics.__init__(new, self.model,
                      None if self._squeeze else self._batch_size,
                      self._device, self._precision, self._task_id,
-                     self._ncon_max, self._build_mode, self._group)
+                     self._ncon_max, self._build_mode, self._group, self._params.per_env)
     new._batch.copy_state_from(self._batch)
+    for name, v in self._params.values.items():
+      new._params.values[name][...] = v
+    for name, v in self._params.derived.items():
+      new._params.derived[name][...] = v
     new._warn_seen = self._warn_seen.copy()
     new._dirty = self._dirty
     new._aux_on = self._aux_on
@@ -658,6 +723,11 @@ class Physics(_control.Physics):
     """
     b = self._batch
     arrays = {name: b.read(field) for name, field in self._CHECKPOINT_FIELDS}
+    if self._params.per_env:      # the block as the device holds it + the fp64 values
+      arrays['modelparam'] = b.read(wrapper.FIELD_MODELPARAM)
+      arrays['per_env'] = np.array(','.join(self._params.per_env))
+      for name in self._params.per_env:
+        arrays['modelparam_' + name] = self._params.values[name]
     np.savez(self._checkpoint_path(path),
              model_hash=np.array(self.model.content_hash()),
              precision=np.array(self._precision),
@@ -683,6 +753,18 @@ class Physics(_control.Physics):
       if z['qpos'].shape != (self.model.nq, self._batch_size):
         raise ValueError('checkpoint holds {} instances, this batch {}'.format(
             z['qpos'].shape[-1], self._batch_size))
+      if not self._params.per_env and 'per_env' in z.files:
+        raise ValueError('checkpoint carries per-env model parameters ({}); this batch '
+                         'was built without per_env and would run the nominal model'
+                         .format(z['per_env']))
+      if self._params.per_env:
+        if ('per_env' not in z.files or
+            str(z['per_env']) != ','.join(self._params.per_env)):
+          raise ValueError('checkpoint was written without the per-env fields of '
+                           'this batch ({})'.format(', '.join(self._params.per_env)))
+        self._batch.write(wrapper.FIELD_MODELPARAM, z['modelparam'])
+        self._params.load_block(
+            z['modelparam'], {n: z['modelparam_' + n] for n in self._params.per_env})
       for name, field in self._CHECKPOINT_FIELDS:
         self._batch.write(field, z[name])
       step_count = int(z['step_count'])

@@ -28,8 +28,10 @@ class VecEnv:
 
   def __init__(self, domain_name, task_name, num_envs, seed=None,
                device=0, precision='f32', torch_io=False, task_kwargs=None,
-               environment_kwargs=None):
+               environment_kwargs=None, per_env=()):
     env_kw = dict(environment_kwargs or {})
+    if per_env:        # model fields read per env (Physics.set_model_params)
+      env_kw['per_env'] = tuple(per_env)
     env_kw.update(batch_size=int(num_envs), device=device,
                   precision=precision, flat_observation=True)
     env_kw.setdefault('device_init', bool(torch_io))

@@ -23,7 +23,8 @@ _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)),
 # enum dmc_field
 (FIELD_QPOS, FIELD_QVEL, FIELD_WARMSTART, FIELD_TIME, FIELD_CTRL, FIELD_OBS,
  FIELD_REWARD, FIELD_SENSORDATA, FIELD_XPOS, FIELD_XMAT, FIELD_QACC,
- FIELD_WARN, FIELD_STATS, FIELD_RETURN, FIELD_TASKDATA) = range(15)
+ FIELD_WARN, FIELD_STATS, FIELD_RETURN, FIELD_TASKDATA,
+ FIELD_MODELPARAM) = range(16)
 
 
 class Error(Exception):
@@ -34,7 +35,8 @@ class ModelInfo(ctypes.Structure):
   _fields_ = [(n, ctypes.c_int) for n in (
       'abi', 'real_size', 'nq', 'nv', 'nu', 'nbody', 'nobs', 'nsensordata',
       'ws_per_env', 'task', 'ncon_max', 'nefc_max', 'integrator', 'npair',
-      'ntaskdata', 'envs_per_block', 'lanes_per_env', 'env_major')]
+      'ntaskdata', 'envs_per_block', 'lanes_per_env', 'env_major',
+      'nmodelparam')]
 
 
 # every symbol declared in include/dmc_hip.h: (restype, argtypes)
@@ -204,6 +206,7 @@ class HipBatch:
         FIELD_XPOS: (i.nbody*3, n), FIELD_XMAT: (i.nbody*9, n),
         FIELD_QACC: (max(i.nv, 1), n), FIELD_WARN: (n,), FIELD_STATS: (3, n),
         FIELD_RETURN: (n,), FIELD_TASKDATA: (max(i.ntaskdata, 1), n),
+        FIELD_MODELPARAM: (max(i.nmodelparam, 1), n),
     }[field]
 
   def _dtype(self, field):

@@ -67,7 +67,12 @@ enum dmc_field {
   DMC_FIELD_TASKDATA = 14,  /* real [ntaskdata][nenv] per-instance task parameters (e.g.
                                the reacher's target position, which the reference
                                writes into model.geom_pos per episode) */
-  DMC_FIELD_COUNT = 15
+  DMC_FIELD_MODELPARAM = 15, /* real [nmodelparam][nenv] model fields that a build reads per
+                               env instead of from its compiled tables (domain
+                               randomisation): rows as laid out by
+                               codegen.model_param_layout; starts with the compiled
+                               model's values, untouched by reset / init_episode */
+  DMC_FIELD_COUNT = 16
 };
 
 enum dmc_warn_bit {
@@ -84,11 +89,15 @@ typedef struct dmc_model_info {
       envs_per_block, /* envs per workgroup of the step kernel */
       lanes_per_env, /* 1, or the group size of a several-lanes-per-env build
                         (8..64; 128 = one env per workgroup of two wavefronts) */
-      env_major;     /* 1: the 2-D state fields are [nenv][k] in HBM (what
+      env_major,     /* 1: the 2-D state fields are [nenv][k] in HBM (what
                         dmc_batch_device_ptr returns); dmc_batch_read and
                         dmc_batch_set_state present [k][nenv] regardless */
+      nmodelparam;   /* rows of DMC_FIELD_MODELPARAM (0: no per-env model fields) */
 } dmc_model_info;
 
+/* 101: dmc_model_info gained `nmodelparam` at its end and DMC_FIELD_MODELPARAM exists; a
+ * caller built against the 100 header must be rebuilt (dmc_model_get_info fills the whole
+ * struct) */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
