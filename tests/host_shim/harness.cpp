@@ -1,38 +1,91 @@
-// Runs dmc_step for ONE env on the host under sanitizers and prints qpos/qvel
-// after each step (compared with the oracle by tests/test_kernel_sanitizers.py).
+// Runs dmc_step of the included kernel source for ONE workgroup on the host
+// under sanitizers, one OS thread per lane (shim.h), and prints every env's
+// qpos/qvel and counters after each step (tests/shim_runner.py compares them
+// with the oracle).  TEST INFRASTRUCTURE ONLY.
+//   stdin: <steps> <nsub>, then per env: <model-parameter block> <qpos> <qvel> <ctrl>
+//   stdout: STEP <t> <env> <qpos> <qvel> | <ncon> <nefc> <iters> <warn>
 #include "shim.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include DMC_KERNEL_SOURCE
 
-int main(int argc, char** argv) {
-  const int steps = argc > 1 ? atoi(argv[1]) : 5;
+// The shape, from what the kernel source defines: the envs of one workgroup of
+// dmc_coop.hip (G lanes each, which never use the workspace: one word per env),
+// else one env, advanced by one lane or by the TEAM lanes of team mode.
+#ifdef DMC_COOP_BUILD
+constexpr int HARNESS_ENVS = EPB, HARNESS_LANES = NTHREADS, HARNESS_WS = EPB;
+static_assert(G == SHIM_GROUP, "shim.h and the kernel source disagree on the group");
+#else
+constexpr int HARNESS_ENVS = 1, HARNESS_LANES = TEAM, HARNESS_WS = WS_WORDS > 0 ? WS_WORDS : 1;
+static_assert(TEAM == SHIM_GROUP, "shim.h and the kernel source disagree on the team");
+#endif
+constexpr int NMP = DMC_NMODELPARAM;
+
+static DmcArgs g_args;
+static void* lane_main(void* arg) {
+  threadIdx.x = (unsigned)(size_t)arg;
+  blockIdx.x = 0;
+  dmc_step(g_args);
+  return nullptr;
+}
+
+int main() {
+  const int n = HARNESS_ENVS;
   const int nq = NQ > 0 ? NQ : 1, nv = NV > 0 ? NV : 1, nu = NU > 0 ? NU : 1;
-  std::vector<real> qpos(nq), qvel(nv, 0), warm(nv, 0), tm(1, 0), ctrl(nu, 0),
-      obs(NOBS > 0 ? NOBS : 1), rew(1), ret(1), sens(NSENSORDATA > 0 ? NSENSORDATA : 1),
-      xpos(NBODY*3), xmat(NBODY*9), qacc(nv),
-      ws((WS_WORDS > 0 ? WS_WORDS : 1));
-  std::vector<unsigned> warn(1, 0);
-  std::vector<int> stats(3, 0);
-  for (int i = 0; i < NQ; i++) qpos[i] = (real)qpos0[i];
-  // optional initial state from argv: qpos then qvel
-  for (int i = 0; i < NQ && 2 + i < argc; i++) qpos[i] = (real)atof(argv[2 + i]);
-  for (int i = 0; i < NV && 2 + NQ + i < argc; i++) qvel[i] = (real)atof(argv[2 + NQ + i]);
-  DmcArgs a;
+  std::vector<real> qpos(nq*n), qvel(nv*n), warm(nv*n, 0), tm(n, 0), ctrl(nu*n),
+      obs((NOBS > 0 ? NOBS : 1)*n), rew(n), ret(n, 0),
+      sens((NSENSORDATA > 0 ? NSENSORDATA : 1)*n), xpos(NBODY*3*n), xmat(NBODY*9*n),
+      qacc(nv*n), ws(HARNESS_WS), mp(NMP*n);
+  std::vector<unsigned> warn(n, 0);
+  std::vector<int> stats(3*n, 0);
+  std::vector<double> in;
+  for (double x; scanf("%lf", &x) == 1;) in.push_back(x);
+  const size_t expected = 2 + (size_t)n*(NMP + NQ + NV + NU);
+  if (in.size() != expected || !feof(stdin)) {
+    fprintf(stderr, "expected %zu numbers (steps nsub, then for each of %d envs %d block + %d qpos + "
+            "%d qvel + %d ctrl), got %zu\n", expected, n, NMP, NQ, NV, NU, in.size());
+    return 2;
+  }
+  const int steps = (int)in[0];
+  const double* at = in.data() + 2;
+  // several-lanes-per-env code objects keep the state env-major: [env][k]
+  for (int e = 0; e < n; e++) {
+    for (int i = 0; i < NMP; i++) mp[e*NMP + i] = (real)*at++;
+    for (int i = 0; i < NQ; i++) qpos[e*nq + i] = (real)*at++;
+    for (int i = 0; i < NV; i++) qvel[e*nv + i] = (real)*at++;
+    for (int i = 0; i < NU; i++) ctrl[e*nu + i] = (real)*at++;   // constant: re-applied from ctrl_store
+  }
+  DmcArgs& a = g_args;
   memset(&a, 0, sizeof a);
-  a.nenv = 1; a.nsub = 1; a.flags = 0;
+  a.nenv = n; a.nsub = (int)in[1]; a.flags = 0;
   a.qpos = qpos.data(); a.qvel = qvel.data(); a.warm = warm.data(); a.time = tm.data();
   a.ctrl_store = ctrl.data(); a.obs = obs.data(); a.obs_sk = 1; a.obs_se = NOBS;
   a.reward = rew.data(); a.episode_return = ret.data(); a.sensordata = sens.data();
   a.xpos = xpos.data(); a.xmat = xmat.data(); a.qacc = qacc.data();
   a.warn = warn.data(); a.stats = stats.data(); a.ws = ws.data();
+  if (NMP > 0) a.modelparam = mp.data();   // else null: a default build that read the block faults
+  if (TEAMED) blockDim.x = TEAM;
+  for (int t = 0; t < HARNESS_LANES/SHIM_GROUP; t++)
+    pthread_barrier_init(&shim_teams[t].bar, nullptr, SHIM_GROUP);
+  pthread_barrier_init(&shim_block_barrier, nullptr, HARNESS_LANES);
+  pthread_attr_t attr;
+  pthread_attr_init(&attr);
+  if (TEAMED) pthread_attr_setstacksize(&attr, 256u << 20);     // the per-lane arrays of a big scene
   for (int t = 0; t < steps; t++) {
-    dmc_step(a);
-    printf("STEP %d", t);
-    for (int i = 0; i < NQ; i++) printf(" %.17g", (double)qpos[i]);
-    for (int i = 0; i < NV; i++) printf(" %.17g", (double)qvel[i]);
-    printf(" | %d %d %d %u\n", stats[0], stats[1], stats[2], warn[0]);
+    if (HARNESS_LANES == 1) {
+      lane_main(nullptr);
+    } else {
+      pthread_t th[HARNESS_LANES];
+      for (size_t i = 0; i < HARNESS_LANES; i++) pthread_create(&th[i], &attr, lane_main, (void*)i);
+      for (int i = 0; i < HARNESS_LANES; i++) pthread_join(th[i], nullptr);
+    }
+    for (int e = 0; e < n; e++) {
+      printf("STEP %d %d", t, e);
+      for (int i = 0; i < NQ; i++) printf(" %.17g", (double)qpos[e*nq + i]);
+      for (int i = 0; i < NV; i++) printf(" %.17g", (double)qvel[e*nv + i]);
+      printf(" | %d %d %d %u\n", stats[3*e], stats[3*e + 1], stats[3*e + 2], warn[e]);
+    }
   }
   return 0;
 }

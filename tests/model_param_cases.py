@@ -77,8 +77,8 @@ SERVO_ARM = """
 ACTUATOR_FIELDS = ('actuator_gear', 'actuator_gainprm', 'actuator_biasprm')
 
 
-def harness_ctrl(nu):
-  """The constant control of tests/host_shim/harness_mp.cpp."""
+def alternating_ctrl(nu):
+  """A constant control of +0.5 and -0.5 in turn."""
   return np.array([-0.5 if i % 2 else 0.5 for i in range(nu)])
 
 

@@ -1,0 +1,142 @@
+"""Driver of the host shim (tests/host_shim): builds harness.cpp around a kernel
+source for a model and a lane shape, runs it, and compares what it prints with
+the fp64 oracle.  Shared by tests/test_kernel_sanitizers.py and
+tests/test_model_params.py.  The shim is test infrastructure: the product path
+cannot reach it."""
+
+import os
+import subprocess
+
+import numpy as np
+
+import helpers
+import kat_models
+import model_param_cases as mpc
+from dm_control_amd import codegen
+from dm_control_amd.mjcf import compiler
+from oracle import oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHIM = os.path.join(ROOT, 'tests', 'host_shim')
+CSRC = os.path.join(ROOT, 'dm_control_amd', 'csrc')
+
+
+def case(name, nenv=None):
+  """(model, task, qpos [n, nq], qvel [n, nv], steps) of `primitives`,
+  `stacked_boxes`, `servo_arm` or a suite model.  nenv None: the env and the
+  step count of the one-env-per-lane tests; else the nenv envs of a workgroup
+  of several lanes per env (those tests bring their own step counts)."""
+  n = nenv or 1
+  if name == 'primitives':
+    model, task, steps = compiler.from_xml_string(kat_models.PRIMITIVES), 0, 40
+    q, v = np.tile(model.qpos0, (n, 1)), np.zeros((n, model.nv))
+    q[:, 2], q[:, 9], q[:, 16] = 0.11, 0.2, 0.3     # stacked, in contact
+  elif name == 'stacked_boxes':
+    model, task, steps = compiler.from_xml_string(kat_models.STACKED_BOXES), 0, 60
+    q = np.tile(model.qpos0, (n, 1))
+    v = 0.3*np.random.RandomState(5).randn(n, model.nv)
+    if nenv is None:
+      q[0, 7 + 3:7 + 7] = [0.98, 0.05, -0.1, 0.15]     # tilt one box: edge contacts too
+      q[0, 7 + 3:7 + 7] /= np.linalg.norm(q[0, 7 + 3:7 + 7])
+  elif name == 'servo_arm':
+    model, task, steps = compiler.from_xml_string(mpc.SERVO_ARM), 0, 60
+    q = np.array([[0.35, -0.6], [-0.3, 0.9]])[:n]     # runs into the limit
+    v = np.array([[1.5, -0.8], [-2.0, 0.5]])[:n]
+  else:
+    model, task, steps = helpers.load_model(name), helpers.TASKS[name], 25
+    if nenv is None:
+      q, v = helpers.initial_states(model, name, 4, seed=7)
+      q, v = q[1:2], v[1:2]
+    else:
+      q, v = helpers.initial_states(model, name, max(n, 2), seed=7)
+      q, v = q[-n:], v[-n:]
+  return model, task, q, v, steps
+
+
+def build(model, task, tmp_path, unroll=True, group=None, team=None, ncon_max=None,
+          per_env=(), sanitizer='address,undefined', f64=True, extra=(), name='harness'):
+  """Compiles tests/host_shim/harness.cpp around the kernel source of the shape:
+  one env per lane (csrc/dmc_kernels.hip; `unroll`), `group` lanes per env
+  (csrc/dmc_coop.hip; 128: 64 lanes and the helper wavefront), or team mode
+  (`team` lanes share the env; `ncon_max`).  sanitizer None: the plain -O2 build
+  without contraction.  Returns the path of the program."""
+  header = tmp_path/'model.h'
+  text = codegen.generate_header(model, task, ncon_max=ncon_max, unroll=unroll, per_env=per_env)
+  header.write_text(text.replace('static __device__ constexpr', 'static constexpr'))
+  if group:
+    shape = ['-DDMC_GROUP=%d' % min(group, 64), '-DDMC_COOP_DUO=%d' % (group == 128)]
+  elif team:
+    shape = ['-DDMC_TEAM=%d' % team]
+  else:
+    shape = ['-DDMC_LDS_BUDGET=16384']
+  if sanitizer:
+    mode = ['-O1', '-g', '-fsanitize=' + sanitizer] + (
+        ['-fno-sanitize-recover=undefined'] if 'undefined' in sanitizer else []) + [
+            '-fno-omit-frame-pointer']
+  else:
+    mode = ['-O2', '-ffp-contract=off']
+  exe = tmp_path/name
+  subprocess.check_call(
+      ['g++', '-std=c++17', '-w', '-pthread'] + mode +
+      (['-DDMC_REAL_IS_DOUBLE'] if f64 else []) + shape + list(extra) + [
+          '-DDMC_MODEL_HEADER="%s"' % header,
+          '-DDMC_KERNEL_SOURCE="%s"' % os.path.join(
+              CSRC, 'dmc_coop.hip' if group else 'dmc_kernels.hip'),
+          '-I', CSRC, '-I', SHIM, '-x', 'c++', os.path.join(SHIM, 'harness.cpp'),
+          '-o', str(exe)])
+  return str(exe)
+
+
+def run(exe, steps, qpos, qvel, ctrl, blocks=None, timeout=600):
+  """Steps the envs qpos[e], qvel[e] (with model-parameter block blocks[e], if
+  the build reads one) under the constant control `ctrl`.  Returns the rows
+  (env, state, (ncon, nefc, iters, warn)) in the order printed."""
+  text = '%d 1\n' % steps
+  for e in range(len(qpos)):
+    values = np.concatenate([[] if blocks is None else blocks[e], qpos[e], qvel[e], ctrl])
+    text += ' '.join('%.17g' % x for x in values) + '\n'
+  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', TSAN_OPTIONS='halt_on_error=1')
+  out = subprocess.run([exe], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       universal_newlines=True, env=env, timeout=timeout)
+  assert out.returncode == 0, out.stderr[-3000:]
+  rows = []
+  for line in out.stdout.splitlines():
+    if line.startswith('STEP'):
+      vals, tail = line.split('|')
+      fields = vals.split()
+      rows.append((int(fields[2]), np.array([float(x) for x in fields[3:]]),
+                   [int(x) for x in tail.split()]))
+  return rows
+
+
+def oracle_at(model, qpos, qvel, ctrl):
+  d = oracle.OracleData(oracle.OracleModel(model))
+  d.qpos[:] = qpos
+  d.qvel[:] = qvel
+  d.ctrl[:] = ctrl
+  d.step1()
+  return d
+
+
+def compare(rows, models, qpos, qvel, ctrl, steps, before_step=None):
+  """Steps the oracle of env e on models[e] next to `rows` and asserts the
+  counters and the state of every row; before_step(d) sees the oracle of a row
+  before it is stepped.  Returns (whether any step had constraint rows, the
+  oracles after the last step)."""
+  datas = [oracle_at(m, qpos[e], qvel[e], ctrl) for e, m in enumerate(models)]
+  touched = False
+  for e, state, (ncon, nefc, iters, warn) in rows:
+    d = datas[e]
+    touched |= d.nefc > 0
+    # contact and row counts as mj_makeConstraint counts them (a pyramid edge
+    # pair that the planar models store as one row still counts as two)
+    assert (ncon, nefc) == (d.ncon, d.nefc)
+    if before_step:
+      before_step(d)
+    d.physics_step()
+    assert warn == 0
+    nq = len(d.qpos)
+    np.testing.assert_allclose(state[:nq], d.qpos, rtol=0, atol=1e-9)
+    np.testing.assert_allclose(state[nq:], d.qvel, rtol=0, atol=1e-8)
+  assert len(rows) == steps*len(models)
+  return touched, datas

@@ -5,62 +5,17 @@ plain C++ through tests/host_shim/shim.h (one lane, one workgroup, fp64) with
 -fsanitize=address,undefined and stepped next to the oracle.  This checks the
 kernel's indexing (static chains, LDS/HBM record tiers, contact list) for
 out-of-bounds and UB, and its arithmetic against the oracle, before anything
-touches the card.  The shim is test infrastructure: the product path cannot
-reach it.
+touches the card.  The shapes of several lanes run one OS thread per lane,
+under ThreadSanitizer too.  Building, running and the comparison with the
+oracle are tests/shim_runner.py; the tests here pass no control (zeros).
 """
-
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers
-import kat_models
-from dm_control_amd import codegen
+import shim_runner
 from dm_control_amd.mjcf import compiler
-from oracle import oracle
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, 'tests', 'host_shim')
-KERNEL = os.path.join(ROOT, 'dm_control_amd', 'csrc', 'dmc_kernels.hip')
-
-
-def _build(model, task, tmp_path, unroll, extra=(), sanitize=True, f64=True,
-           name='harness'):
-  header = tmp_path/'model.h'
-  text = codegen.generate_header(model, task, unroll=unroll)
-  header.write_text(text.replace('static __device__ constexpr',
-                                 'static constexpr'))
-  exe = tmp_path/name
-  mode = (['-O1', '-g', '-fsanitize=address,undefined',
-           '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer']
-          if sanitize else ['-O2', '-ffp-contract=off'])
-  cmd = ['g++', '-std=c++17', '-w'] + mode + (
-      ['-DDMC_REAL_IS_DOUBLE'] if f64 else []) + [
-         '-DDMC_LDS_BUDGET=16384'] + list(extra) + [
-         '-DDMC_MODEL_HEADER="%s"' % header,
-         '-DDMC_KERNEL_SOURCE="%s"' % KERNEL,
-         '-I', os.path.join(ROOT, 'dm_control_amd', 'csrc'), '-I', SHIM,
-         '-x', 'c++', os.path.join(SHIM, 'harness.cpp'), '-o', str(exe)]
-  subprocess.check_call(cmd)
-  return str(exe)
-
-
-def _run(exe, steps, qpos, qvel):
-  args = [exe, str(steps)] + ['%.17g' % v for v in qpos] + \
-         ['%.17g' % v for v in qvel]
-  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
-  out = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       universal_newlines=True, env=env, timeout=600)
-  assert out.returncode == 0, out.stderr[-3000:]
-  rows = []
-  for line in out.stdout.splitlines():
-    if line.startswith('STEP'):
-      vals, tail = line.split('|')
-      rows.append((np.array([float(v) for v in vals.split()[2:]]),
-                   [int(v) for v in tail.split()]))
-  return rows
 
 
 @pytest.mark.timeout(900)
@@ -79,40 +34,11 @@ def _run(exe, steps, qpos, qvel):
     # box-box (face contacts), capsule-box and plane-box in one stack
     ('stacked_boxes', True, ()), ('stacked_boxes', False, ())])
 def test_kernel_source_is_clean_and_matches_oracle(name, unroll, extra, tmp_path):
-  if name == 'primitives':
-    model, task = compiler.from_xml_string(kat_models.PRIMITIVES), 0
-    qpos, qvel = model.qpos0.copy(), np.zeros(model.nv)
-    qpos[2], qpos[9], qpos[16] = 0.11, 0.2, 0.3     # stacked, in contact
-    steps = 40
-  elif name == 'stacked_boxes':
-    model, task = compiler.from_xml_string(kat_models.STACKED_BOXES), 0
-    qpos, qvel = model.qpos0.copy(), np.zeros(model.nv)
-    qpos[7 + 3:7 + 7] = [0.98, 0.05, -0.1, 0.15]     # tilt one box: edge contacts too
-    qpos[7 + 3:7 + 7] /= np.linalg.norm(qpos[7 + 3:7 + 7])
-    qvel[:] = 0.3*np.random.RandomState(5).randn(model.nv)
-    steps = 60
-  else:
-    model, task = helpers.load_model(name), helpers.TASKS[name]
-    q, v = helpers.initial_states(model, name, 4, seed=7)
-    qpos, qvel = q[1], v[1]
-    steps = 25
-  exe = _build(model, task, tmp_path, unroll, extra)
-  rows = _run(exe, steps, qpos, qvel)
-  assert len(rows) == steps
-  d = oracle.OracleData(oracle.OracleModel(model))
-  d.qpos[:] = qpos
-  d.qvel[:] = qvel
-  d.step1()
-  touched = False
-  for state, (ncon, nefc, iters, warn) in rows:
-    touched |= d.nefc > 0
-    # contact and row counts as mj_makeConstraint counts them (a pyramid edge
-    # pair that the planar models store as one row still counts as two)
-    assert (ncon, nefc) == (d.ncon, d.nefc)
-    d.physics_step()
-    assert warn == 0
-    np.testing.assert_allclose(state[:model.nq], d.qpos, rtol=0, atol=1e-9)
-    np.testing.assert_allclose(state[model.nq:], d.qvel, rtol=0, atol=1e-8)
+  model, task, q, v, steps = shim_runner.case(name)
+  ctrl = np.zeros(model.nu)
+  exe = shim_runner.build(model, task, tmp_path, unroll=unroll, extra=extra)
+  rows = shim_runner.run(exe, steps, q, v, ctrl)
+  touched, _ = shim_runner.compare(rows, [model], q, v, ctrl, steps)
   # constraint rows (LDS and HBM tiers) were exercised (the cart-pole: RK4 path)
   assert touched or name == 'cartpole'
 
@@ -127,16 +53,13 @@ def test_mixed_precision_source_beats_plain_fp32_on_the_smooth_system(tmp_path):
   and within BASELINE's 1e-4."""
   model, task = helpers.load_model('cartpole'), helpers.TASKS['cartpole']
   q, v = helpers.initial_states(model, 'cartpole', 8, seed=3)
-  exes = {tag: _build(model, task, tmp_path, True, extra, sanitize=False,
-                      f64=False, name=tag)
+  ctrl = np.zeros(model.nu)
+  exes = {tag: shim_runner.build(model, task, tmp_path, sanitizer=None, f64=False,
+                                 extra=extra, name=tag)
           for tag, extra in (('f32', ()), ('mixed', ('-DDMC_STATE_COMP=1',)))}
-  om = oracle.OracleModel(model)
   worse = 0
   for e in range(4):
-    d = oracle.OracleData(om)
-    d.qpos[:] = q[e]
-    d.qvel[:] = v[e]
-    d.step1()
+    d = shim_runner.oracle_at(model, q[e], v[e], ctrl)
     ref = []
     for _ in range(1000):
       d.physics_step()
@@ -144,7 +67,8 @@ def test_mixed_precision_source_beats_plain_fp32_on_the_smooth_system(tmp_path):
     ref = np.array(ref)
     err = {}
     for tag, exe in exes.items():
-      st = np.array([r[0][:model.nq] for r in _run(exe, 1000, q[e], v[e])])
+      rows = shim_runner.run(exe, 1000, q[e:e + 1], v[e:e + 1], ctrl)
+      st = np.array([state[:model.nq] for _, state, _ in rows])
       err[tag] = np.abs(st - ref).max(axis=1)/np.maximum(1, np.abs(ref).max(axis=1))
     assert err['mixed'][-1] <= 1e-4
     assert err['mixed'][:100].max() <= 1e-6
@@ -155,29 +79,6 @@ def test_mixed_precision_source_beats_plain_fp32_on_the_smooth_system(tmp_path):
 # ---------------------------------------------------------------------------
 # several lanes per env (csrc/dmc_coop.hip): one OS thread per lane
 # ---------------------------------------------------------------------------
-COOP_KERNEL = os.path.join(ROOT, 'dm_control_amd', 'csrc', 'dmc_coop.hip')
-
-
-def _build_coop(model, task, tmp_path, sanitizer, group):
-  header = tmp_path/'model.h'
-  text = codegen.generate_header(model, task, unroll=True)
-  header.write_text(text.replace('static __device__ constexpr',
-                                 'static constexpr'))
-  exe = tmp_path/'harness_coop'
-  cmd = ['g++', '-std=c++17', '-O1', '-g', '-pthread',
-         '-fsanitize=' + sanitizer, '-fno-omit-frame-pointer',
-         '-DDMC_REAL_IS_DOUBLE', '-DDMC_GROUP=%d' % min(group, 64),
-         '-DDMC_COOP_DUO=%d' % (group == 128),
-         '-DDMC_MODEL_HEADER="%s"' % header,
-         '-DDMC_KERNEL_SOURCE="%s"' % COOP_KERNEL,
-         '-I', os.path.join(ROOT, 'dm_control_amd', 'csrc'), '-I', SHIM,
-         '-x', 'c++', os.path.join(SHIM, 'harness_coop.cpp'), '-o', str(exe)]
-  if 'undefined' in sanitizer:
-    cmd.insert(1, '-fno-sanitize-recover=undefined')
-  subprocess.check_call(cmd)
-  return str(exe)
-
-
 @pytest.mark.timeout(1200)
 @pytest.mark.parametrize('name,sanitizer,group,steps', [
     ('humanoid', 'address,undefined', 64, 9),
@@ -200,59 +101,16 @@ def _build_coop(model, task, tmp_path, sanitizer, group):
     ('walker', 'thread', 16, 8),
     ('walker', 'address,undefined', 8, 8)])
 def test_several_lanes_per_env_source(name, sanitizer, group, steps, tmp_path):
-  """csrc/dmc_coop.hip with one thread per lane (tests/host_shim/shim_coop.h):
+  """csrc/dmc_coop.hip with one thread per lane (tests/host_shim/shim.h):
   a phase hand-over is a pthread barrier, so ThreadSanitizer reports any LDS
   word that crosses lanes without one, AddressSanitizer every index; the
   trajectories of all envs of the workgroup are compared with the oracle."""
   nenv = max(1, 64//group)      # group 128: one env, two wavefronts
-  if name == 'primitives':
-    model, task = compiler.from_xml_string(kat_models.PRIMITIVES), 0
-    q = np.tile(model.qpos0, (nenv, 1))
-    v = np.zeros((nenv, model.nv))
-    q[:, 2], q[:, 9], q[:, 16] = 0.11, 0.2, 0.3
-  elif name == 'stacked_boxes':
-    model, task = compiler.from_xml_string(kat_models.STACKED_BOXES), 0
-    q = np.tile(model.qpos0, (nenv, 1))
-    v = 0.3*np.random.RandomState(5).randn(nenv, model.nv)
-  else:
-    model, task = helpers.load_model(name), helpers.TASKS[name]
-    q, v = helpers.initial_states(model, name, max(nenv, 2), seed=7)
-    q, v = q[-nenv:], v[-nenv:]
-  exe = _build_coop(model, task, tmp_path, sanitizer, group)
-  args = [exe, str(steps), '1']
-  for e in range(nenv):
-    args += ['%.17g' % x for x in q[e]] + ['%.17g' % x for x in v[e]]
-  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0',
-             TSAN_OPTIONS='halt_on_error=1')
-  out = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       universal_newlines=True, env=env, timeout=1100)
-  assert out.returncode == 0, out.stderr[-3000:]
-  om = oracle.OracleModel(model)
-  datas = []
-  for e in range(nenv):
-    d = oracle.OracleData(om)
-    d.qpos[:] = q[e]
-    d.qvel[:] = v[e]
-    d.step1()
-    datas.append(d)
-  seen, touched = 0, False
-  for line in out.stdout.splitlines():
-    if not line.startswith('STEP'):
-      continue
-    vals, tail = line.split('|')
-    fields = vals.split()
-    e = int(fields[2])
-    state = np.array([float(x) for x in fields[3:]])
-    ncon, nefc, iters, warn = [int(x) for x in tail.split()]
-    d = datas[e]
-    touched |= d.nefc > 0
-    assert (ncon, nefc) == (d.ncon, d.nefc)
-    d.physics_step()
-    assert warn == 0
-    np.testing.assert_allclose(state[:model.nq], d.qpos, rtol=0, atol=1e-9)
-    np.testing.assert_allclose(state[model.nq:], d.qvel, rtol=0, atol=1e-8)
-    seen += 1
-  assert seen == steps*nenv
+  model, task, q, v, _ = shim_runner.case(name, nenv)
+  ctrl = np.zeros(model.nu)
+  exe = shim_runner.build(model, task, tmp_path, group=group, sanitizer=sanitizer)
+  rows = shim_runner.run(exe, steps, q, v, ctrl, timeout=1100)
+  touched, _ = shim_runner.compare(rows, [model]*nenv, q, v, ctrl, steps)
   assert touched or name == 'cartpole'
 
 
@@ -260,25 +118,6 @@ def test_several_lanes_per_env_source(name, sanitizer, group, steps, tmp_path):
 # team mode of csrc/dmc_kernels.hip (one wavefront per env, big scenes): one OS
 # thread per lane, a phase boundary (tsync) is a pthread barrier
 # ---------------------------------------------------------------------------
-def _build_team(model, tmp_path, sanitizer, team, ncon_max=64):
-  header = tmp_path/'model.h'
-  text = codegen.generate_header(model, 0, ncon_max=ncon_max, unroll=False)
-  header.write_text(text.replace('static __device__ constexpr',
-                                 'static constexpr'))
-  exe = tmp_path/'harness_team'
-  cmd = ['g++', '-std=c++17', '-w', '-O1', '-g', '-pthread',
-         '-fsanitize=' + sanitizer, '-fno-omit-frame-pointer',
-         '-DDMC_REAL_IS_DOUBLE', '-DDMC_TEAM=%d' % team,
-         '-DDMC_MODEL_HEADER="%s"' % header,
-         '-DDMC_KERNEL_SOURCE="%s"' % KERNEL,
-         '-I', os.path.join(ROOT, 'dm_control_amd', 'csrc'), '-I', SHIM,
-         '-x', 'c++', os.path.join(SHIM, 'harness_team.cpp'), '-o', str(exe)]
-  if 'undefined' in sanitizer:
-    cmd.insert(1, '-fno-sanitize-recover=undefined')
-  subprocess.check_call(cmd)
-  return str(exe)
-
-
 def _team_scene(name):
   """Scenes of several humanoids and a ball with contacts BETWEEN kinematic
   trees (the coupled blocks of the Hessian): two walkers pushed into each other
@@ -319,33 +158,17 @@ def test_team_build_of_a_scene_with_several_trees(name, sanitizer, team, steps, 
   oracle's -- with contacts between trees, so the coupled blocks of the Newton
   Hessian (rows left of a tree's tile) are factored and solved too."""
   m, qpos, qvel = _team_scene(name)
-  exe = _build_team(m, tmp_path, sanitizer, team)
-  args = [exe, str(steps)] + ['%.17g' % x for x in qpos] + ['%.17g' % x for x in qvel]
-  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0', TSAN_OPTIONS='halt_on_error=1')
-  out = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       universal_newlines=True, env=env, timeout=1400)
-  assert out.returncode == 0, out.stderr[-3000:]
-  om = oracle.OracleModel(m)
-  d = oracle.OracleData(om)
-  d.qpos[:] = qpos
-  d.qvel[:] = qvel
-  d.step1()
-  seen, coupled = 0, False
+  ctrl = np.zeros(m.nu)
+  exe = shim_runner.build(m, 0, tmp_path, unroll=False, team=team, ncon_max=64,
+                          sanitizer=sanitizer)
+  rows = shim_runner.run(exe, steps, qpos[None], qvel[None], ctrl, timeout=1400)
   tree_of_dof = np.asarray(m.body_rootid)[np.asarray(m.dof_bodyid)]
-  for line in out.stdout.splitlines():
-    if not line.startswith('STEP'):
-      continue
-    vals, tail = line.split('|')
-    state = np.array([float(x) for x in vals.split()[2:]])
-    ncon, nefc, iters, warn = [int(x) for x in tail.split()]
-    assert (ncon, nefc) == (d.ncon, d.nefc)
+  coupled = []
+
+  def rows_across_trees(d):
     J = np.asarray(d.efc_J_matrix())[:d.nefc] if callable(getattr(d, 'efc_J_matrix', None)) else None
     if J is not None:
-      coupled |= any(len(set(tree_of_dof[np.nonzero(row)[0]])) > 1 for row in J)
-    d.physics_step()
-    assert warn == 0
-    np.testing.assert_allclose(state[:m.nq], d.qpos, rtol=0, atol=1e-9)
-    np.testing.assert_allclose(state[m.nq:], d.qvel, rtol=0, atol=1e-8)
-    seen += 1
-  assert seen == steps
-  assert coupled, 'no constraint row touched two trees: the scene does not test the coupling'
+      coupled.append(any(len(set(tree_of_dof[np.nonzero(row)[0]])) > 1 for row in J))
+
+  shim_runner.compare(rows, [m], qpos[None], qvel[None], ctrl, steps, before_step=rows_across_trees)
+  assert any(coupled), 'no constraint row touched two trees: the scene does not test the coupling'

@@ -4,23 +4,15 @@ the host under sanitizers next to the oracle, and the Python surface against a
 stub batch.  The expected trajectory of an env is always the fp64 oracle on a
 deepcopy of the model with that env's values."""
 
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import helpers
-import kat_models
 import model_param_cases as mpc
+import shim_runner
 from dm_control_amd import build
 from dm_control_amd import codegen
-from dm_control_amd.mjcf import compiler
-from oracle import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, 'tests', 'host_shim')
-CSRC = os.path.join(ROOT, 'dm_control_amd', 'csrc')
 ALL = mpc.ALL_FIELDS
 
 
@@ -89,102 +81,17 @@ def test_unknown_field_and_team_mode_raise():
 # ---------------------------------------------------------------------------
 # 3. the kernel sources on the host (ASan + UBSan, fp64) next to the oracle
 # ---------------------------------------------------------------------------
-def _header(model, task, tmp_path, unroll, per_env):
-  header = tmp_path/'model.h'
-  text = codegen.generate_header(model, task, unroll=unroll, per_env=per_env)
-  header.write_text(text.replace('static __device__ constexpr', 'static constexpr'))
-  return header
-
-
-def _build_one_lane(model, task, tmp_path, unroll, per_env):
-  header = _header(model, task, tmp_path, unroll, per_env)
-  exe = tmp_path/'harness_mp'
-  subprocess.check_call(
-      ['g++', '-std=c++17', '-w', '-O1', '-g', '-fsanitize=address,undefined',
-       '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer',
-       '-DDMC_REAL_IS_DOUBLE', '-DDMC_LDS_BUDGET=16384',
-       '-DDMC_MODEL_HEADER="%s"' % header,
-       '-DDMC_KERNEL_SOURCE="%s"' % os.path.join(CSRC, 'dmc_kernels.hip'),
-       '-I', CSRC, '-I', SHIM, '-x', 'c++', os.path.join(SHIM, 'harness_mp.cpp'),
-       '-o', str(exe)])
-  return str(exe)
-
-
-def _build_coop(model, task, tmp_path, group, per_env):
-  header = _header(model, task, tmp_path, True, per_env)
-  exe = tmp_path/'harness_coop_mp'
-  subprocess.check_call(
-      ['g++', '-fno-sanitize-recover=undefined', '-std=c++17', '-O1', '-g', '-pthread',
-       '-fsanitize=address,undefined', '-fno-omit-frame-pointer',
-       '-DDMC_REAL_IS_DOUBLE', '-DDMC_GROUP=%d' % min(group, 64),
-       '-DDMC_COOP_DUO=%d' % (group == 128),
-       '-DDMC_MODEL_HEADER="%s"' % header,
-       '-DDMC_KERNEL_SOURCE="%s"' % os.path.join(CSRC, 'dmc_coop.hip'),
-       '-I', CSRC, '-I', SHIM, '-x', 'c++', os.path.join(SHIM, 'harness_coop_mp.cpp'),
-       '-o', str(exe)])
-  return str(exe)
-
-
-def _fmt(values):
-  return ['%.17g' % v for v in np.asarray(values, float).ravel()]
-
-
-def _steps_of(stdout, has_env):
-  for line in stdout.splitlines():
-    if line.startswith('STEP'):
-      vals, tail = line.split('|')
-      f = vals.split()
-      e = int(f[2]) if has_env else 0
-      yield e, np.array([float(x) for x in f[3 if has_env else 2:]]), [int(x) for x in tail.split()]
-
-
-def _oracle_at(model, qpos, qvel):
-  d = oracle.OracleData(oracle.OracleModel(model))
-  d.qpos[:] = qpos
-  d.qvel[:] = qvel
-  d.ctrl[:] = mpc.harness_ctrl(model.nu)
-  d.step1()
-  return d
-
-
-def _check_next_to_oracle(rows, models, nominal, q, v, steps):
-  """rows: (env, state, (ncon, nefc, iters, warn)) in step order.  models[e]: the
-  perturbed copy of env e.  Bounds of tests/test_kernel_sanitizers.py."""
-  nq = nominal.nq
-  datas = [_oracle_at(m, q[e], v[e]) for e, m in enumerate(models)]
-  plain = [_oracle_at(nominal, q[e], v[e]) for e in range(len(models))]
-  seen, touched = 0, False
-  for e, state, (ncon, nefc, iters, warn) in rows:
-    d = datas[e]
-    touched |= d.nefc > 0
-    assert (ncon, nefc) == (d.ncon, d.nefc)
-    d.physics_step()
-    assert warn == 0
-    np.testing.assert_allclose(state[:nq], d.qpos, rtol=0, atol=1e-9)
-    np.testing.assert_allclose(state[nq:], d.qvel, rtol=0, atol=1e-8)
-    seen += 1
-  assert seen == steps*len(models)
+def _check_next_to_oracle(rows, models, nominal, q, v, ctrl, steps):
+  """rows of shim_runner.run.  models[e]: the perturbed copy of env e."""
+  touched, datas = shim_runner.compare(rows, models, q, v, ctrl, steps)
   assert touched
   # not vacuous: the perturbed and the nominal model have moved apart
   for e, d in enumerate(datas):
+    plain = shim_runner.oracle_at(nominal, q[e], v[e], ctrl)
     for _ in range(steps):
-      plain[e].physics_step()
-    gap = max(np.abs(plain[e].qpos - d.qpos).max(), np.abs(plain[e].qvel - d.qvel).max())
+      plain.physics_step()
+    gap = max(np.abs(plain.qpos - d.qpos).max(), np.abs(plain.qvel - d.qvel).max())
     assert gap > 1e-6, 'env %d: perturbed and nominal oracle differ by %g only' % (e, gap)
-
-
-def _case(name):
-  if name == 'primitives':
-    model, task = compiler.from_xml_string(kat_models.PRIMITIVES), 0
-    qpos, qvel = model.qpos0.copy(), np.zeros(model.nv)
-    qpos[2], qpos[9], qpos[16] = 0.11, 0.2, 0.3     # stacked, in contact
-    return model, task, qpos, qvel, 40
-  if name == 'servo_arm':
-    model = compiler.from_xml_string(mpc.SERVO_ARM)
-    return model, 0, np.array([0.35, -0.6]), np.array([1.5, -0.8]), 60   # runs into the limit
-  model, task = helpers.load_model(name), helpers.TASKS[name]
-  q, v = helpers.initial_states(model, name, 4, seed=7)
-  return model, task, q[1], v[1], 25
 
 
 @pytest.mark.timeout(900)
@@ -199,17 +106,15 @@ def _case(name):
     [('servo_arm', True, ('actuator_biasprm',)), ('servo_arm', True, mpc.ACTUATOR_FIELDS),
      ('servo_arm', False, mpc.ACTUATOR_FIELDS), ('servo_arm', True, ALL)])
 def test_one_lane_source_reads_the_block(name, unroll, fields, tmp_path):
-  model, task, qpos, qvel, steps = _case(name)
+  model, task, q, v, steps = shim_runner.case(name)
   assert np.any(getattr(model, fields[0]) if fields[0] != 'gravity' else model.opt.gravity)
   p = mpc.perturbed(model, np.random.RandomState(23), fields)
   layout = codegen.model_param_layout(model, fields)
-  exe = _build_one_lane(model, task, tmp_path, unroll, fields)
-  args = [exe, str(steps)] + _fmt(mpc.block_of(p, layout)) + _fmt(qpos) + _fmt(qvel)
-  out = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       universal_newlines=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS='detect_leaks=0'))
-  assert out.returncode == 0, out.stderr[-3000:]
-  _check_next_to_oracle(list(_steps_of(out.stdout, False)), [p], model, [qpos], [qvel], steps)
+  # a constant, non-zero control: the actuator rows matter
+  ctrl = mpc.alternating_ctrl(model.nu)
+  exe = shim_runner.build(model, task, tmp_path, unroll=unroll, per_env=fields)
+  rows = shim_runner.run(exe, steps, q, v, ctrl, blocks=[mpc.block_of(p, layout)])
+  _check_next_to_oracle(rows, [p], model, q, v, ctrl, steps)
 
 
 @pytest.mark.timeout(1200)
@@ -217,30 +122,20 @@ def test_one_lane_source_reads_the_block(name, unroll, fields, tmp_path):
                                               ('cheetah', 32, 12), ('servo_arm', 64, 40),
                                               ('servo_arm', 32, 40)])
 def test_several_lanes_source_reads_the_block(name, group, steps, tmp_path):
-  """csrc/dmc_coop.hip through shim_coop.h, every env of the workgroup with its
-  own parameters (one env per wavefront, with the helper wavefront, two envs
-  per wavefront)."""
+  """csrc/dmc_coop.hip through the host shim, every env of the workgroup with
+  its own parameters (one env per wavefront, with the helper wavefront, two envs
+  per wavefront).  The servo arm's actuators have a bias term: every actuator
+  row is read."""
   nenv = max(1, 64//group)
-  if name == 'servo_arm':       # actuators with a bias term: every actuator row is read
-    model, task = compiler.from_xml_string(mpc.SERVO_ARM), 0
-    q = np.array([[0.35, -0.6], [-0.3, 0.9]])[:nenv]
-    v = np.array([[1.5, -0.8], [-2.0, 0.5]])[:nenv]
-  else:
-    model, task = helpers.load_model(name), helpers.TASKS[name]
-    q, v = helpers.initial_states(model, name, max(nenv, 2), seed=7)
-    q, v = q[-nenv:], v[-nenv:]
+  model, task, q, v, _ = shim_runner.case(name, nenv)
   rs = np.random.RandomState(23)
   models = [mpc.perturbed(model, rs) for _ in range(nenv)]
   layout = codegen.model_param_layout(model, ALL)
-  exe = _build_coop(model, task, tmp_path, group, ALL)
-  args = [exe, str(steps), '1']
-  for e in range(nenv):
-    args += _fmt(mpc.block_of(models[e], layout)) + _fmt(q[e]) + _fmt(v[e])
-  out = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       universal_newlines=True, timeout=1100,
-                       env=dict(os.environ, ASAN_OPTIONS='detect_leaks=0'))
-  assert out.returncode == 0, out.stderr[-3000:]
-  _check_next_to_oracle(list(_steps_of(out.stdout, True)), models, model, q, v, steps)
+  ctrl = mpc.alternating_ctrl(model.nu)
+  exe = shim_runner.build(model, task, tmp_path, group=group, per_env=ALL)
+  rows = shim_runner.run(exe, steps, q, v, ctrl, timeout=1100,
+                         blocks=[mpc.block_of(m, layout) for m in models])
+  _check_next_to_oracle(rows, models, model, q, v, ctrl, steps)
 
 
 # ---------------------------------------------------------------------------
