@@ -140,7 +140,8 @@ void fill_args(dmc_batch* b, DmcArgs& a) {
 
 extern "C" {
 
-int dmc_version(void) { return 101; }   // 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM
+// 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM; 102: dmc_model_info.seq_launch
+int dmc_version(void) { return 102; }
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -344,6 +345,7 @@ int load_model(const char* path, const void* image, int device_id, dmc_model** o
   i.env_major = raw[15] != 0;
   i.ntaskdata = raw[16];
   i.nmodelparam = raw[18] > 0 ? raw[18] : 0;
+  i.seq_launch = raw[19] == 1;
   *out = m;
   return 0;
 }
@@ -543,11 +545,15 @@ int dmc_batch_forward(dmc_batch* b, int count_contacts) {
   return launch(b, b->model->k_observe, a, b->model->info.lanes_per_env);
 }
 
-int dmc_batch_step(dmc_batch* b, const void* ctrl, long long stride_k,
-                   long long stride_env, int on_device, int nsub,
-                   int want_outputs) {
-  if (!b) return fail("null batch");
-  if (nsub < 0) return fail("nsub must be >= 0");
+}  // extern "C"
+
+namespace {
+
+// one launch of dmc_step: `nsteps` control steps (more than one only on a code
+// object with `seq_launch`), step t reading its controls at ctrl + t*stride_t
+int step_launch(dmc_batch* b, const void* ctrl, long long stride_k,
+                long long stride_env, long long stride_t, int nsteps, int on_device,
+                int nsub, int want_outputs) {
   HIP_TRY(hipSetDevice(b->model->device));
   const dmc_model_info& i = b->model->info;
   DmcArgs a;
@@ -577,9 +583,23 @@ int dmc_batch_step(dmc_batch* b, const void* ctrl, long long stride_k,
     a.ctrl_sk = stride_k;
     a.ctrl_se = stride_env;
   }
+  a.nsteps = nsteps;
+  a.ctrl_st = stride_t;
   if (launch(b, b->model->k_step, a, b->model->info.lanes_per_env)) return -1;
-  if (b->timing) b->launches++;
+  if (b->timing) b->launches += nsteps;   // (the timer's average stays per control step)
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmc_batch_step(dmc_batch* b, const void* ctrl, long long stride_k,
+                   long long stride_env, int on_device, int nsub,
+                   int want_outputs) {
+  if (!b) return fail("null batch");
+  if (nsub < 0) return fail("nsub must be >= 0");
+  return step_launch(b, ctrl, stride_k, stride_env, 0, 1, on_device, nsub, want_outputs);
 }
 
 int dmc_batch_step_n(dmc_batch* b, const void* ctrl, long long stride_k,
@@ -588,11 +608,20 @@ int dmc_batch_step_n(dmc_batch* b, const void* ctrl, long long stride_k,
   if (!b) return fail("null batch");
   if (!ctrl) return fail("dmc_batch_step_n: device controls required");
   if (nsteps < 0) return fail("nsteps must be >= 0");
-  const size_t rs = (size_t)b->model->info.real_size;
-  for (int t = 0; t < nsteps; t++)
-    if (dmc_batch_step(b, (const char*)ctrl + (size_t)t*(size_t)stride_t*rs, stride_k,
-                       stride_env, 1, nsub, want_outputs))
+  if (nsub < 0) return fail("nsub must be >= 0");
+  const long long rs = (long long)b->model->info.real_size;
+  // One launch per chunk of control steps where the code object loops over them
+  // itself (bounded, so that no launch occupies a shared device for long), else
+  // one launch per step.  DMC_STEP_STALE_FIRST is about the sequence's first step.
+  const int chunk_max = b->model->info.seq_launch ? DMC_SEQ_LAUNCH_MAX_STEPS : 1;
+  for (int t = 0; t < nsteps;) {
+    const int chunk = nsteps - t < chunk_max ? nsteps - t : chunk_max;
+    if (step_launch(b, (const char*)ctrl + (long long)t*stride_t*rs, stride_k, stride_env,
+                    stride_t, chunk, 1, nsub,
+                    t == 0 ? want_outputs : want_outputs & ~DMC_STEP_STALE_FIRST))
       return -1;
+    t += chunk;
+  }
   return 0;
 }
 

@@ -31,6 +31,11 @@ struct DmcArgs {
   DMC_REALPTR taskdata;    // [NTASKDATA][nenv] per-instance task parameters
   double task_param_r[4];
   DMC_REALPTR modelparam;  // [NMODELPARAM][nenv] model fields read per env (builds with per-env fields)
+  // sequence launch (one-env-per-lane dmc_step of code objects that report it in
+  // dmc_info): control steps in this launch, step t reading its controls at
+  // ctrl + t*ctrl_st.  A zero-filled block (nsteps 0) is one step.
+  int nsteps;
+  long long ctrl_st;
 };
 // dmc_step flags
 #define DMC_FLAG_CTRL 1          // ctrl pointer valid (else reuse ctrl_store)

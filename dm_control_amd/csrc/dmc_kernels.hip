@@ -4696,27 +4696,11 @@ DEV void store_env(const Env& E, const DmcArgs& a, int e, real time) {
 // coalesced stores.  Other layouts (explicit strides) are written directly.
 constexpr bool OBS_STAGE_FITS = !TEAMED && LDS_WORDS >= LANES*(NOBS > 0 ? NOBS : 1);
 
-DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
+// hands over what the task layer computed for the state in E: observation,
+// reward, sensors, aux frames, stats (not the episode return)
+DEV void write_outputs(const Env& E, const DmcArgs& a, int e, const real* obs, real rew,
                        real* lds_base) {
   const long long n = a.nenv;
-  if (TEAMED && TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0) {
-    // no task: the observation is the (shared) state, every lane copies its share
-    tsync();
-    for (int k = tlane(); k < NQ; k += TEAM)
-      a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se] = E.qpos[k];
-    for (int k = tlane(); k < NV; k += TEAM)
-      a.obs[(long long)(NQ + k)*a.obs_sk + (long long)e*a.obs_se] = E.qvel[k];
-    if (tlane() == 0) {
-      a.reward[e] = 0;
-      if (a.xpos) for (int i = 0; i < NBODY*3; i++) a.xpos[i*n + e] = E.xpos[i];
-      if (a.xmat) for (int i = 0; i < NBODY*9; i++) a.xmat[i*n + e] = E.xmat[i];
-      a.stats[e] = E.ncon; a.stats[n + e] = E.nefc + E.nmerged; a.stats[2*n + e] = E.iters;
-    }
-    return;
-  }
-  real obs[NOBS > 0 ? NOBS : 1];
-  const real rew = task_outputs(E, a, obs);
-  if (TEAMED && tlane() != 0) return;
   if (OBS_STAGE_FITS && a.obs_sk == 1 && a.obs_se == NOBS) {
     const int lane = threadIdx.x;
     DMC_UNROLL
@@ -4735,7 +4719,6 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
       a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se] = obs[k];
   }
   a.reward[e] = rew;
-  if (accumulate) a.episode_return[e] += rew;
   DMC_UNROLL
   for (int s = 0; s < NSENSOR; s++) {
     const int adr = sensor_adr[s], o = sensor_objid[s];
@@ -4764,8 +4747,45 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
   a.stats[e] = E.ncon; a.stats[n + e] = E.nefc + E.nmerged; a.stats[2*n + e] = E.iters;
 }
 
-// nsub x Physics.step, then observation + reward of the new state.
+DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
+                       real* lds_base) {
+  const long long n = a.nenv;
+  if (TEAMED && TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0) {
+    // no task: the observation is the (shared) state, every lane copies its share
+    tsync();
+    for (int k = tlane(); k < NQ; k += TEAM)
+      a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se] = E.qpos[k];
+    for (int k = tlane(); k < NV; k += TEAM)
+      a.obs[(long long)(NQ + k)*a.obs_sk + (long long)e*a.obs_se] = E.qvel[k];
+    if (tlane() == 0) {
+      a.reward[e] = 0;
+      if (a.xpos) for (int i = 0; i < NBODY*3; i++) a.xpos[i*n + e] = E.xpos[i];
+      if (a.xmat) for (int i = 0; i < NBODY*9; i++) a.xmat[i*n + e] = E.xmat[i];
+      a.stats[e] = E.ncon; a.stats[n + e] = E.nefc + E.nmerged; a.stats[2*n + e] = E.iters;
+    }
+    return;
+  }
+  real obs[NOBS > 0 ? NOBS : 1];
+  const real rew = task_outputs(E, a, obs);
+  if (TEAMED && tlane() != 0) return;
+  write_outputs(E, a, e, obs, rew, lds_base);
+  if (accumulate) a.episode_return[e] += rew;
+}
+
+// nsteps x (nsub x Physics.step, then observation + reward of the new state).
 // flags bit0: ctrl given (else reuse ctrl_store); bit1: skip outputs (settle)
+//
+// Sequence launch (one env per lane; a.nsteps control steps, 0 = 1): the state,
+// the warm start, the episode return and the low words of the `mixed` state stay
+// in registers from step to step; step t reads its controls at ctrl + t*ctrl_st.
+// Every step runs the observation stage and the task layer (the reward of each
+// step enters the episode return, with the same sequential adds as one launch
+// per step), but only the last step's outputs are written: nobody can read the
+// ones in between.  The frames the observation stage computes for the state
+// after step t are the ones step t+1's forward pass opens with, but that pass
+// computes them again: skipping them was measured and dropped (the two inlined
+// copies round differently, and keeping the frames live across the loop spilled
+// 50 VGPRs in the cheetah build).  Team mode takes one step per launch.
 #ifndef DMC_WAVES_PER_EU
 #define DMC_WAVES_PER_EU 1
 #endif
@@ -4782,60 +4802,80 @@ dmc_step(DmcArgs a) {
       : Work{lds_rows + threadIdx.x, a.ws + e, n};
   team_bind(E, W);
   load_env(E, a, e, time);
-  if (TEAMED) {
-    // (a lane applies the actuators i = lane mod TEAM: it fetches those controls)
-    const int tl = tlane();
-    bool bc = false;
-    for (int i = tl; i < NU; i += TEAM) {
-      E.ctrl[i] = (a.flags & 1) ? a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se] : a.ctrl_store[i*n + e];
-      bc |= bad(E.ctrl[i]);
-    }
-    if ((a.flags & 1) && tany(bc)) {
-      E.warn |= WARN_BADCTRL;
-      for (int i = tl; i < NU; i += TEAM) E.ctrl[i] = 0;
-    }
-    if (a.flags & 1)
-      for (int i = tl; i < NU; i += TEAM) a.ctrl_store[i*n + e] = E.ctrl[i];
-  } else if (a.flags & 1) {
-    bool bc = false;
-    DMC_UNROLL
-    for (int i = 0; i < NU; i++) {
-      E.ctrl[i] = a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se];
-      bc |= bad(E.ctrl[i]);
-    }
-    if (bc) {   // mj_fwdActuation's ctrl check: warn and zero the controls
-      E.warn |= WARN_BADCTRL;
-      DMC_UNROLL
-      for (int i = 0; i < NU; i++) E.ctrl[i] = 0;
-    }
-    if (!TEAMED || tlane() == 0)
-    DMC_UNROLL
-    for (int i = 0; i < NU; i++) a.ctrl_store[i*n + e] = E.ctrl[i];
-  } else {
-    DMC_UNROLL
-    for (int i = 0; i < NU; i++) E.ctrl[i] = a.ctrl_store[i*n + e];
-  }
   const real tol = R(tolerance_opt > DMC_TOL_FLOOR ? tolerance_opt : DMC_TOL_FLOOR);
+  const int nsteps = (TEAMED || a.nsteps < 1) ? 1 : a.nsteps;
+  const bool outputs = !(a.flags & DMC_FLAG_NO_OUTPUT);
+  // the observation stage computes the frames (a model without a task: the
+  // observation is qpos and qvel; the frames are only recomputed if someone reads them)
+  const bool frames = !(TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0 && !a.xpos && !a.xmat);
+  real ret = 0;               // register copy of the episode return
+  if (!TEAMED && outputs) ret = a.episode_return[e];
 #ifdef DMC_STEP_PROFILE
   const long long tk_ = wall_clock64();
 #endif
-  for (int s = 0; s < a.nsub; s++)
-    physics_step(E, W, time, tol, s == 0 && (a.flags & DMC_FLAG_STALE_FIRST));
+  for (int t = 0; t < nsteps; t++) {
+    if (TEAMED) {
+      // (a lane applies the actuators i = lane mod TEAM: it fetches those controls)
+      const int tl = tlane();
+      bool bc = false;
+      for (int i = tl; i < NU; i += TEAM) {
+        E.ctrl[i] = (a.flags & 1) ? a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se] : a.ctrl_store[i*n + e];
+        bc |= bad(E.ctrl[i]);
+      }
+      if ((a.flags & 1) && tany(bc)) {
+        E.warn |= WARN_BADCTRL;
+        for (int i = tl; i < NU; i += TEAM) E.ctrl[i] = 0;
+      }
+      if (a.flags & 1)
+        for (int i = tl; i < NU; i += TEAM) a.ctrl_store[i*n + e] = E.ctrl[i];
+    } else if (a.flags & 1) {
+      const real* ctrl = a.ctrl + (long long)t*a.ctrl_st;
+      bool bc = false;
+      DMC_UNROLL
+      for (int i = 0; i < NU; i++) {
+        E.ctrl[i] = ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se];
+        bc |= bad(E.ctrl[i]);
+      }
+      if (bc) {   // mj_fwdActuation's ctrl check: warn and zero the controls
+        E.warn |= WARN_BADCTRL;
+        DMC_UNROLL
+        for (int i = 0; i < NU; i++) E.ctrl[i] = 0;
+      }
+    } else if (t == 0) {
+      DMC_UNROLL
+      for (int i = 0; i < NU; i++) E.ctrl[i] = a.ctrl_store[i*n + e];
+    }
+    for (int s = 0; s < a.nsub; s++)
+      physics_step(E, W, time, tol, t == 0 && s == 0 && (a.flags & DMC_FLAG_STALE_FIRST));
+    if (outputs) {
+#ifndef DMC_ABLATE_OBS
+      if (!frames) check_state(E, time);
+      else observe_stage(E, time);
+#endif
+      if (TEAMED) store_outputs(E, a, e, true, lds_rows);
+      else if (t < nsteps - 1) {    // a step nobody observes: its reward alone is kept
+        real obs[NOBS > 0 ? NOBS : 1];
+        ret += task_outputs(E, a, obs);
+      }
+    }
+  }
 #ifdef DMC_STEP_PROFILE
   E.prof[7] = (real)(wall_clock64() - tk_);      // all substeps
 #endif
+  if (!TEAMED && (a.flags & 1)) {      // data.ctrl: the controls of the last step
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) a.ctrl_store[i*n + e] = E.ctrl[i];
+  }
   if (a.qacc && (!TEAMED || tlane() == 0)) {
     DMC_UNROLL
     for (int i = 0; i < NV; i++) a.qacc[i*n + e] = E.qacc[i];
   }
-  if (!(a.flags & 2)) {
-#ifndef DMC_ABLATE_OBS
-    // (a model without a task: the observation is qpos and qvel; the frames are
-    // only recomputed if someone reads them)
-    if (TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0 && !a.xpos && !a.xmat) check_state(E, time);
-    else observe_stage(E, time);
-#endif
-    store_outputs(E, a, e, true, lds_rows);
+  if (!TEAMED && outputs) {      // the last step's outputs
+    real obs[NOBS > 0 ? NOBS : 1];
+    const real rew = task_outputs(E, a, obs);
+    ret += rew;
+    write_outputs(E, a, e, obs, rew, lds_rows);
+    a.episode_return[e] = ret;
   }
 #ifdef DMC_SOLVER_PROFILE
   __syncthreads();
@@ -5010,5 +5050,6 @@ extern "C" __device__ const int dmc_info[20] = {
                                 threads unless a team of lanes shares an env);
                                 the workspace is sized for the batch rounded up to this*/,
     DMC_ENV_MAJOR /*0: state fields are [k][env]*/, NTASKDATA,
-    LANES /*threads per workgroup*/, DMC_NMODELPARAM /*rows of the model-parameter block*/, 0};
+    LANES /*threads per workgroup*/, DMC_NMODELPARAM /*rows of the model-parameter block*/,
+    TEAMED ? 0 : 1 /*dmc_step runs DmcArgs.nsteps control steps per launch*/};
 #endif

@@ -36,7 +36,7 @@ class ModelInfo(ctypes.Structure):
       'abi', 'real_size', 'nq', 'nv', 'nu', 'nbody', 'nobs', 'nsensordata',
       'ws_per_env', 'task', 'ncon_max', 'nefc_max', 'integrator', 'npair',
       'ntaskdata', 'envs_per_block', 'lanes_per_env', 'env_major',
-      'nmodelparam')]
+      'nmodelparam', 'seq_launch')]
 
 
 # every symbol declared in include/dmc_hip.h: (restype, argtypes)

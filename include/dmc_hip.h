@@ -92,12 +92,15 @@ typedef struct dmc_model_info {
       env_major,     /* 1: the 2-D state fields are [nenv][k] in HBM (what
                         dmc_batch_device_ptr returns); dmc_batch_read and
                         dmc_batch_set_state present [k][nenv] regardless */
-      nmodelparam;   /* rows of DMC_FIELD_MODELPARAM (0: no per-env model fields) */
+      nmodelparam,   /* rows of DMC_FIELD_MODELPARAM (0: no per-env model fields) */
+      seq_launch;    /* 1: the step kernel runs a whole sequence of control steps per
+                        launch (dmc_batch_step_n); 0: one launch per control step */
 } dmc_model_info;
 
 /* 101: dmc_model_info gained `nmodelparam` at its end and DMC_FIELD_MODELPARAM exists; a
  * caller built against the 100 header must be rebuilt (dmc_model_get_info fills the whole
- * struct) */
+ * struct)
+ * 102: dmc_model_info gained `seq_launch` at its end (same rule) */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
@@ -179,8 +182,16 @@ int dmc_batch_step(dmc_batch* batch, const void* ctrl, long long stride_k,
 /* `nsteps` control steps back to back on the batch's stream, step t reading
  * its controls at ctrl + t*stride_t reals (device memory): the n_sub_steps loop
  * of control.Environment.step (rl/control.py:101-102) over a pre-computed action
- * sequence (open-loop rollouts, benchmarks) without a host round trip per step;
- * the observation / reward fields hold those of the last step */
+ * sequence (open-loop rollouts, benchmarks; stride_t = 0: action repeat) without
+ * a host round trip per step.  The observation / reward / sensor / stats fields
+ * hold those of the last step, DMC_FIELD_RETURN has every step's reward added,
+ * DMC_STEP_STALE_FIRST applies to the first step.  Same results, bit for bit, as
+ * `nsteps` calls of dmc_batch_step.  On a code object with
+ * dmc_model_info.seq_launch this is one launch per chunk of at most
+ * DMC_SEQ_LAUNCH_MAX_STEPS control steps (state, warm start and episode return
+ * stay in registers in between; outputs are written once per chunk); otherwise
+ * one launch per control step.  The batch timer counts control steps either way. */
+#define DMC_SEQ_LAUNCH_MAX_STEPS 64
 int dmc_batch_step_n(dmc_batch* batch, const void* ctrl, long long stride_k,
                      long long stride_env, long long stride_t, int nsteps,
                      int nsub, int want_outputs);
