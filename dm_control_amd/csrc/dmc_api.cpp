@@ -64,7 +64,7 @@ struct dmc_batch {
   hipStream_t own_stream = nullptr;   // created with the batch
   void* field[DMC_FIELD_COUNT] = {};
   size_t bytes[DMC_FIELD_COUNT] = {};
-  size_t rows[DMC_FIELD_COUNT] = {};   // k extent of a [k][nenv] field (1: per-env scalar)
+  size_t rows[DMC_FIELD_COUNT] = {};   // k extent of the field (1: per-env scalar)
   size_t elem[DMC_FIELD_COUNT] = {};   // bytes per element
   void* ws = nullptr;
   void* ctrl_staging = nullptr;   // device copy of host-provided controls
@@ -80,28 +80,73 @@ struct dmc_batch {
 
 namespace {
 
-int launch(dmc_batch* b, hipFunction_t fn, DmcArgs& args, int group = -1) {
+// Every dmc_field, in enum order: what dmc_batch_create allocates and what
+// read / write / set_state may do with it.
+enum Kind { REAL, INT32, UINT32 };
+struct Field {
+  dmc_field id;
+  int dmc_model_info::*count;   // the member that counts the rows (nullptr: one)
+  int mult;                     // rows per count
+  bool pad;                     // an empty count still has one row
+  Kind kind;
+  bool writable;   // by dmc_batch_write: the state, task data, model parameters and
+                   // what else a checkpoint restores (control, return, warning mask)
+  bool agent;      // [nenv][k] in every code object, never flipped
+};
+using Info = dmc_model_info;
+constexpr Field FIELDS[] = {
+    {DMC_FIELD_QPOS, &Info::nq, 1, true, REAL, true, false},
+    {DMC_FIELD_QVEL, &Info::nv, 1, true, REAL, true, false},
+    {DMC_FIELD_WARMSTART, &Info::nv, 1, true, REAL, true, false},
+    {DMC_FIELD_TIME, nullptr, 1, false, REAL, true, false},
+    {DMC_FIELD_CTRL, &Info::nu, 1, true, REAL, true, false},
+    {DMC_FIELD_OBS, &Info::nobs, 1, true, REAL, false, true},
+    {DMC_FIELD_REWARD, nullptr, 1, false, REAL, false, false},
+    {DMC_FIELD_SENSORDATA, &Info::nsensordata, 1, true, REAL, false, false},
+    {DMC_FIELD_XPOS, &Info::nbody, 3, false, REAL, false, false},
+    {DMC_FIELD_XMAT, &Info::nbody, 9, false, REAL, false, false},
+    {DMC_FIELD_QACC, &Info::nv, 1, true, REAL, false, false},
+    {DMC_FIELD_WARN, nullptr, 1, false, UINT32, true, false},
+    {DMC_FIELD_STATS, nullptr, 3, false, INT32, false, false},
+    {DMC_FIELD_RETURN, nullptr, 1, false, REAL, true, false},
+    {DMC_FIELD_TASKDATA, &Info::ntaskdata, 1, true, REAL, true, false},
+    {DMC_FIELD_MODELPARAM, &Info::nmodelparam, 1, true, REAL, true, false},
+};
+static_assert(sizeof FIELDS/sizeof FIELDS[0] == DMC_FIELD_COUNT, "one row per dmc_field");
+constexpr bool fields_in_enum_order(int f = 0) {
+  return f == DMC_FIELD_COUNT || (FIELDS[f].id == f && fields_in_enum_order(f + 1));
+}
+static_assert(fields_in_enum_order(), "FIELDS[f] describes field f");
+
+// code objects with env-major state keep a 2-D field as [nenv][k] in HBM while
+// the ABI presents [k][nenv]
+bool flipped(const dmc_batch* b, int f) {
+  return b->model->info.env_major && !FIELDS[f].agent && b->rows[f] > 1;
+}
+
+enum Shape { TASK_SETUP, MODEL_SHAPED };
+
+int launch(dmc_batch* b, hipFunction_t fn, DmcArgs& args, Shape shape) {
   size_t size = sizeof(DmcArgs);
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                     HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  // Workgroup = one wavefront.  `group` lanes advance one env together (the
-  // code object reports its shape in dmc_info); `group` < 0: the task-setup
-  // kernel, always one env per lane of a full wave.
+  // TASK_SETUP (dmc_init_episode): always one env per lane of a full wave.
+  // MODEL_SHAPED (dmc_step, dmc_observe): the shape the code object reports in
+  // dmc_info -- envs_per_block envs per workgroup, lanes_per_env lanes each (one
+  // lane, a group within a wavefront, or two wavefronts per env).
   const dmc_model_info& mi = b->model->info;
   unsigned block = 64, per_block = 64;
-  if (group > 1) {   // several lanes per env: 64 threads, or two wavefronts per env
+  if (shape == MODEL_SHAPED) {
     per_block = (unsigned)mi.envs_per_block;
     block = (unsigned)(mi.lanes_per_env*mi.envs_per_block);
   }
-  else if (group == 1) { block = per_block = (unsigned)mi.envs_per_block; }
   const unsigned grid = (unsigned)((b->nenv + per_block - 1)/per_block);
   HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, b->stream,
                                 nullptr, config));
   return 0;
 }
 
-// [rows][n] <-> [n][rows] on the host (elements of `elem` bytes): code objects
-// with env-major state keep [nenv][k] in HBM while the ABI presents [k][nenv]
+// [rows][n] <-> [n][rows] on the host (elements of `elem` bytes), see `flipped`
 void transpose_host(const char* src, char* dst, size_t src_rows, size_t src_cols,
                     size_t elem) {
   for (size_t r = 0; r < src_rows; r++)
@@ -325,27 +370,27 @@ int load_model(const char* path, const void* image, int device_id, dmc_model** o
   hipDeviceptr_t dptr = nullptr;
   size_t bytes = 0;
   err = hipModuleGetGlobal(&dptr, &bytes, m->module, "dmc_info");
-  int raw[20] = {0};
-  if (err == hipSuccess && bytes >= sizeof raw)
-    err = hipMemcpy(raw, dptr, sizeof raw, hipMemcpyDeviceToHost);
-  if (err != hipSuccess || raw[0] != 1) {
+  DmcInfo d{};
+  if (err == hipSuccess && bytes >= sizeof d)
+    err = hipMemcpy(&d, dptr, sizeof d, hipMemcpyDeviceToHost);
+  if (err != hipSuccess || d.abi != 1) {
     (void)hipModuleUnload(m->module);
     delete m;
     return fail("code object %s has no valid dmc_info table", path);
   }
   dmc_model_info& i = m->info;
-  i.abi = raw[0]; i.real_size = raw[1]; i.nq = raw[2]; i.nv = raw[3];
-  i.nu = raw[4]; i.nbody = raw[5]; i.nobs = raw[6]; i.nsensordata = raw[7];
-  i.ws_per_env = raw[8]; i.task = raw[9]; i.ncon_max = raw[10];
-  i.nefc_max = raw[11]; i.integrator = raw[12]; i.npair = raw[13];
-  // raw[14] envs per workgroup, raw[17] threads per workgroup: one env per lane
-  // (64, 32 or 16 envs in a 64-wide wave) or a group of lanes per env
-  i.envs_per_block = raw[14] > 0 ? raw[14] : 64;
-  i.lanes_per_env = raw[17] > i.envs_per_block ? raw[17]/i.envs_per_block : 1;
-  i.env_major = raw[15] != 0;
-  i.ntaskdata = raw[16];
-  i.nmodelparam = raw[18] > 0 ? raw[18] : 0;
-  i.seq_launch = raw[19] == 1;
+  i.abi = d.abi; i.real_size = d.real_size; i.nq = d.nq; i.nv = d.nv;
+  i.nu = d.nu; i.nbody = d.nbody; i.nobs = d.nobs; i.nsensordata = d.nsensordata;
+  i.ws_per_env = d.ws_per_env; i.task = d.task; i.ncon_max = d.ncon_max;
+  i.nefc_max = d.nefc_max; i.integrator = d.integrator; i.npair = d.npair;
+  i.ntaskdata = d.ntaskdata;
+  // one env per lane (64, 32 or 16 envs in a 64-wide wave) or a group of lanes per env
+  i.envs_per_block = d.envs_per_block > 0 ? d.envs_per_block : 64;
+  i.lanes_per_env = d.threads_per_block > i.envs_per_block
+                        ? d.threads_per_block/i.envs_per_block : 1;
+  i.env_major = d.env_major != 0;
+  i.nmodelparam = d.nmodelparam > 0 ? d.nmodelparam : 0;
+  i.seq_launch = d.seq_launch == 1;
   *out = m;
   return 0;
 }
@@ -378,27 +423,13 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   const dmc_model_info& i = model->info;
   const size_t rs = (size_t)i.real_size, n = (size_t)nenv;
   auto atleast1 = [](int v) { return (size_t)(v > 0 ? v : 1); };
-  b->bytes[DMC_FIELD_QPOS] = atleast1(i.nq)*n*rs;
-  b->bytes[DMC_FIELD_QVEL] = atleast1(i.nv)*n*rs;
-  b->bytes[DMC_FIELD_WARMSTART] = atleast1(i.nv)*n*rs;
-  b->bytes[DMC_FIELD_TIME] = n*rs;
-  b->bytes[DMC_FIELD_CTRL] = atleast1(i.nu)*n*rs;
-  b->bytes[DMC_FIELD_OBS] = atleast1(i.nobs)*n*rs;
-  b->bytes[DMC_FIELD_REWARD] = n*rs;
-  b->bytes[DMC_FIELD_SENSORDATA] = atleast1(i.nsensordata)*n*rs;
-  b->bytes[DMC_FIELD_XPOS] = (size_t)i.nbody*3*n*rs;
-  b->bytes[DMC_FIELD_XMAT] = (size_t)i.nbody*9*n*rs;
-  b->bytes[DMC_FIELD_QACC] = atleast1(i.nv)*n*rs;
-  b->bytes[DMC_FIELD_WARN] = n*sizeof(unsigned);
-  b->bytes[DMC_FIELD_STATS] = 3*n*sizeof(int);
-  b->bytes[DMC_FIELD_RETURN] = n*rs;
-  b->bytes[DMC_FIELD_TASKDATA] = atleast1(i.ntaskdata)*n*rs;
-  b->bytes[DMC_FIELD_MODELPARAM] = atleast1(i.nmodelparam)*n*rs;
   for (int f = 0; f < DMC_FIELD_COUNT; f++) {
-    b->elem[f] = (f == DMC_FIELD_WARN || f == DMC_FIELD_STATS) ? sizeof(int) : rs;
-    b->rows[f] = b->bytes[f]/(n*b->elem[f]);
+    const Field& d = FIELDS[f];
+    const size_t count = !d.count ? 1 : d.pad ? atleast1(i.*d.count) : (size_t)(i.*d.count);
+    b->rows[f] = count*(size_t)d.mult;
+    b->elem[f] = d.kind == REAL ? rs : d.kind == INT32 ? sizeof(int) : sizeof(unsigned);
+    b->bytes[f] = b->rows[f]*n*b->elem[f];
   }
-  b->rows[DMC_FIELD_OBS] = 1;   // agent layout [nenv][nobs] in every code object
   hipError_t err = hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking);
   b->stream = b->own_stream;
   for (int f = 0; f < DMC_FIELD_COUNT && err == hipSuccess; f++) {
@@ -424,7 +455,7 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
     DmcArgs a;
     fill_args(b, a);
     a.flags = DMC_FLAG_RESET_ONLY | DMC_FLAG_TASKDATA_DEFAULT;
-    if (launch(b, model->k_init, a)) return -1;
+    if (launch(b, model->k_init, a, TASK_SETUP)) return -1;
   }
   return dmc_batch_reset(b);
 }
@@ -462,12 +493,12 @@ int dmc_batch_reset(dmc_batch* b) {
   if (!b) return fail("null batch");
   HIP_TRY(hipSetDevice(b->model->device));
   // mj_resetData: an init_episode launch with a task-less code path would
-  // need the model tables; instead run dmc_init_episode with TASK bits
-  // masked off via flags=16 (reset only).
+  // need the model tables; instead run dmc_init_episode with the task's part
+  // masked off via DMC_FLAG_RESET_ONLY.
   DmcArgs a;
   fill_args(b, a);
   a.flags = DMC_FLAG_RESET_ONLY;
-  if (launch(b, b->model->k_init, a)) return -1;
+  if (launch(b, b->model->k_init, a, TASK_SETUP)) return -1;
   HIP_TRY(hipMemsetAsync(b->field[DMC_FIELD_WARN], 0, b->bytes[DMC_FIELD_WARN],
                          b->stream));
   HIP_TRY(hipMemsetAsync(b->field[DMC_FIELD_STATS], 0,
@@ -486,7 +517,7 @@ int dmc_batch_set_state(dmc_batch* b, const void* qpos, const void* qvel,
   for (auto& it : items) {
     if (!it.src) continue;
     const void* src = it.src;
-    if (b->model->info.env_major && b->rows[it.f] > 1) {
+    if (flipped(b, it.f)) {
       tmp.resize(b->bytes[it.f]);
       transpose_host((const char*)it.src, tmp.data(), b->rows[it.f],
                      (size_t)b->nenv, b->elem[it.f]);
@@ -501,20 +532,14 @@ int dmc_batch_set_state(dmc_batch* b, const void* qpos, const void* qvel,
 
 int dmc_batch_write(dmc_batch* b, int field, const void* src, size_t bytes) {
   if (!b || !src) return fail("dmc_batch_write: null argument");
-  // the integration state, the per-instance task data and model parameters, and what a checkpoint
-  // must restore besides (last applied control, episode return, warning mask)
-  if (field != DMC_FIELD_QPOS && field != DMC_FIELD_QVEL &&
-      field != DMC_FIELD_WARMSTART && field != DMC_FIELD_TIME &&
-      field != DMC_FIELD_TASKDATA && field != DMC_FIELD_MODELPARAM &&
-      field != DMC_FIELD_CTRL &&
-      field != DMC_FIELD_RETURN && field != DMC_FIELD_WARN)
+  if (field < 0 || field >= DMC_FIELD_COUNT || !FIELDS[field].writable)
     return fail("dmc_batch_write: field %d is not writable", field);
   if (bytes != b->bytes[field])
     return fail("dmc_batch_write: field %d has %zu bytes, caller passed %zu",
                 field, b->bytes[field], bytes);
   HIP_TRY(hipSetDevice(b->model->device));
   std::vector<char> tmp;
-  if (b->model->info.env_major && b->rows[field] > 1) {
+  if (flipped(b, field)) {
     tmp.resize(bytes);
     transpose_host((const char*)src, tmp.data(), b->rows[field], (size_t)b->nenv,
                    b->elem[field]);
@@ -533,7 +558,7 @@ int dmc_batch_init_episode(dmc_batch* b, uint64_t seed, int only_colliding) {
   fill_args(b, a);
   a.seed = seed;
   a.flags = only_colliding ? DMC_FLAG_ONLY_COLLIDING : 0;
-  return launch(b, b->model->k_init, a);
+  return launch(b, b->model->k_init, a, TASK_SETUP);
 }
 
 int dmc_batch_forward(dmc_batch* b, int count_contacts) {
@@ -542,7 +567,7 @@ int dmc_batch_forward(dmc_batch* b, int count_contacts) {
   DmcArgs a;
   fill_args(b, a);
   a.flags = count_contacts ? DMC_FLAG_COUNT_CONTACTS : 0;
-  return launch(b, b->model->k_observe, a, b->model->info.lanes_per_env);
+  return launch(b, b->model->k_observe, a, MODEL_SHAPED);
 }
 
 }  // extern "C"
@@ -585,7 +610,7 @@ int step_launch(dmc_batch* b, const void* ctrl, long long stride_k,
   }
   a.nsteps = nsteps;
   a.ctrl_st = stride_t;
-  if (launch(b, b->model->k_step, a, b->model->info.lanes_per_env)) return -1;
+  if (launch(b, b->model->k_step, a, MODEL_SHAPED)) return -1;
   if (b->timing) b->launches += nsteps;   // (the timer's average stays per control step)
   return 0;
 }
@@ -637,7 +662,7 @@ int dmc_batch_read(dmc_batch* b, int field, void* dst, size_t bytes) {
     return fail("dmc_batch_read: field %d has %zu bytes, caller asked for %zu",
                 field, b->bytes[field], bytes);
   HIP_TRY(hipSetDevice(b->model->device));
-  const bool flip = b->model->info.env_major && b->rows[field] > 1;
+  const bool flip = flipped(b, field);
   std::vector<char> tmp(flip ? bytes : 0);
   HIP_TRY(hipMemcpyAsync(flip ? (void*)tmp.data() : dst, b->field[field], bytes,
                          hipMemcpyDeviceToHost, b->stream));

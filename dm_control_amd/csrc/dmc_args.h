@@ -1,7 +1,8 @@
-// dmc_args.h -- kernel argument block shared by the host runtime
-// (dmc_api.cpp) and the device code (dmc_kernels.hip).  Plain pointers and
-// sizes only; `real`-typed arrays are void* on the host side because the
-// element type (float/double) is a property of the loaded code object.
+// dmc_args.h -- the whole contract between the host runtime (dmc_api.cpp) and
+// the device code (dmc_kernels.hip, dmc_coop.hip): the kernel argument block,
+// the bits of its `flags`, and the code object's self-description `dmc_info`.
+// Plain pointers and sizes only; `real`-typed arrays are void* on the host side
+// because the element type (float/double) is a property of the loaded code object.
 #pragma once
 #ifndef DMC_REALPTR
 #define DMC_REALPTR void*
@@ -37,7 +38,7 @@ struct DmcArgs {
   int nsteps;
   long long ctrl_st;
 };
-// dmc_step flags
+// bits of DmcArgs.flags
 #define DMC_FLAG_CTRL 1          // ctrl pointer valid (else reuse ctrl_store)
 #define DMC_FLAG_NO_OUTPUT 2     // skip observation/reward (settle steps)
 #define DMC_FLAG_COUNT_CONTACTS 4
@@ -45,3 +46,23 @@ struct DmcArgs {
 #define DMC_FLAG_RESET_ONLY 16     // dmc_init_episode: mj_resetData only
 #define DMC_FLAG_TASKDATA_DEFAULT 32  // dmc_init_episode: task data and model parameters <- model values
 #define DMC_FLAG_STALE_FIRST 64    // dmc_step: first substep takes its acceleration from the reset state
+
+// `dmc_info`: what a code object says about itself, read by dmc_api.cpp through
+// hipModuleGetGlobal.  The member order is the layout in the code object; new
+// members go at the end (an older code object then reads as 0 there).  Aligned as
+// the compiler aligns the `int[20]` it used to be, so that it stays where it was.
+struct alignas(16) DmcInfo {
+  int abi;                // 1
+  int real_size;          // sizeof(real)
+  int nq, nv, nu, nbody, nobs, nsensordata;
+  int ws_per_env;         // workspace reals per env
+  int task, ncon_max, nefc_max, integrator, npair;
+  int envs_per_block;     // envs per workgroup of dmc_step / dmc_observe (0: 64); the
+                          // workspace is sized for the batch rounded up to this
+  int env_major;          // 0: the 2-D state fields are [k][env] in HBM; else [env][k]
+  int ntaskdata;
+  int threads_per_block;  // = envs_per_block unless several lanes share an env
+  int nmodelparam;        // rows of the model-parameter block
+  int seq_launch;         // 1: dmc_step runs DmcArgs.nsteps control steps per launch
+};
+static_assert(sizeof(DmcInfo) == 20*sizeof(int), "dmc_info is 20 ints");

@@ -1855,7 +1855,7 @@ dmc_step(DmcArgs a) {
     return;
   }
   C.load(a, e);
-  if (a.flags & 1) {
+  if (a.flags & DMC_FLAG_CTRL) {
     bool bc = false;
     for (int i = l; i < NU; i += G) {
       const real c = a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se];
@@ -1878,7 +1878,7 @@ dmc_step(DmcArgs a) {
   { const long long t_ = wall_clock64(); C.tprof[PH_EULER] += t_ - C.tlast; C.tlast = t_; }
 #endif
   if (a.qacc) for (int i = l; i < NV; i += G) a.qacc[sidx(i, e, n, NVX)] = S[off::QACC + i];
-  if (!(a.flags & 2)) {
+  if (!(a.flags & DMC_FLAG_NO_OUTPUT)) {
     C.observe_stage();
     C.outputs(a, e, true);
   }
@@ -1933,7 +1933,7 @@ dmc_observe(DmcArgs a) {
   C.observe_stage();
   if (NTOUCH > 0) {
     C.ncon = ncon_forward; C.nefc = nefc_forward;
-  } else if (a.flags & 4) {   // count contacts (humanoid reset rejection test)
+  } else if (a.flags & DMC_FLAG_COUNT_CONTACTS) {   // count contacts (humanoid reset rejection test)
     C.ncon = 0; C.nefc = 0;
     if (NPAIR > 0) C.detect_contacts();
   }
@@ -1941,9 +1941,10 @@ dmc_observe(DmcArgs a) {
   C.store(a, e);
 }
 
-extern "C" __device__ const int dmc_info[20] = {
-    1 /*abi*/, (int)sizeof(real), NQ, NV, NU, NBODY, NOBS, NSENSORDATA,
-    1 /*workspace reals per env: none, everything is in LDS*/, TASK, NCON_MAX, NEFC_MAX,
-    INTEGRATOR, NPAIR, EPB /*envs per 64-lane workgroup*/,
-    DMC_ENV_MAJOR /*state fields are [env][k]*/, NTASKDATA, NTHREADS /*threads per workgroup*/,
-    DMC_NMODELPARAM /*rows of the model-parameter block*/, 0};
+extern "C" __device__ const DmcInfo dmc_info = {
+    .abi = 1, .real_size = (int)sizeof(real), .nq = NQ, .nv = NV, .nu = NU, .nbody = NBODY,
+    .nobs = NOBS, .nsensordata = NSENSORDATA,
+    .ws_per_env = 1,   // none, everything is in LDS
+    .task = TASK, .ncon_max = NCON_MAX, .nefc_max = NEFC_MAX, .integrator = INTEGRATOR,
+    .npair = NPAIR, .envs_per_block = EPB, .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA,
+    .threads_per_block = NTHREADS, .nmodelparam = DMC_NMODELPARAM, .seq_launch = 0};

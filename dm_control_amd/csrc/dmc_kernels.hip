@@ -266,7 +266,7 @@ DEV T tsum(T x) {
   for (int m = TEAM/2; m > 0; m >>= 1) x += txor(x, m);
   return x;
 }
-#elif defined(DMC_TEAM)      // host shim: one OS thread per lane (tests/host_shim/shim_coop.h)
+#elif defined(DMC_TEAM)      // host shim: one OS thread per lane (tests/host_shim/shim.h)
 DEV int tlane() { return shim_lane(); }
 DEV void tsync() { gsync(); }
 template <class T> DEV T txor(T x, int m) { return gxor(x, m); }
@@ -4819,16 +4819,16 @@ dmc_step(DmcArgs a) {
       const int tl = tlane();
       bool bc = false;
       for (int i = tl; i < NU; i += TEAM) {
-        E.ctrl[i] = (a.flags & 1) ? a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se] : a.ctrl_store[i*n + e];
+        E.ctrl[i] = (a.flags & DMC_FLAG_CTRL) ? a.ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se] : a.ctrl_store[i*n + e];
         bc |= bad(E.ctrl[i]);
       }
-      if ((a.flags & 1) && tany(bc)) {
+      if ((a.flags & DMC_FLAG_CTRL) && tany(bc)) {
         E.warn |= WARN_BADCTRL;
         for (int i = tl; i < NU; i += TEAM) E.ctrl[i] = 0;
       }
-      if (a.flags & 1)
+      if (a.flags & DMC_FLAG_CTRL)
         for (int i = tl; i < NU; i += TEAM) a.ctrl_store[i*n + e] = E.ctrl[i];
-    } else if (a.flags & 1) {
+    } else if (a.flags & DMC_FLAG_CTRL) {
       const real* ctrl = a.ctrl + (long long)t*a.ctrl_st;
       bool bc = false;
       DMC_UNROLL
@@ -4862,7 +4862,7 @@ dmc_step(DmcArgs a) {
 #ifdef DMC_STEP_PROFILE
   E.prof[7] = (real)(wall_clock64() - tk_);      // all substeps
 #endif
-  if (!TEAMED && (a.flags & 1)) {      // data.ctrl: the controls of the last step
+  if (!TEAMED && (a.flags & DMC_FLAG_CTRL)) {      // data.ctrl: the controls of the last step
     DMC_UNROLL
     for (int i = 0; i < NU; i++) a.ctrl_store[i*n + e] = E.ctrl[i];
   }
@@ -4915,7 +4915,7 @@ dmc_observe(DmcArgs a) {
   observe_stage(E, time);
   if (NTOUCH > 0) {
     E.ncon = ncon_forward; E.nefc = nefc_forward;
-  } else if (a.flags & 4) {   // count contacts (humanoid reset rejection test)
+  } else if (a.flags & DMC_FLAG_COUNT_CONTACTS) {   // count contacts (humanoid reset rejection test)
     E.ncon = 0; E.nefc = 0; E.nmerged = 0;
     if (NPAIR > 0) detect_contacts(E, W);
   }
@@ -4952,7 +4952,7 @@ dmc_init_episode(DmcArgs a) {
   const int e = blockIdx.x*blockDim.x + threadIdx.x;   // one env per lane in every build
   if (e >= a.nenv) return;
   const long long n = a.nenv;
-  if ((a.flags & 8) && a.stats[sidx(0, e, n, 3)] == 0) return;
+  if ((a.flags & DMC_FLAG_ONLY_COLLIDING) && a.stats[sidx(0, e, n, 3)] == 0) return;
   Rng rng = {a.seed*0x2545F4914F6CDD1DULL + (uint64_t)e, 0};
   real qpos[NQ > 0 ? NQ : 1], qvel[NVX];
   DMC_UNROLL
@@ -5042,14 +5042,13 @@ dmc_init_episode(DmcArgs a) {
 }
 
 #ifndef DMC_COOP_BUILD
-// self-description read by dmc_api.cpp through hipModuleGetGlobal
-extern "C" __device__ const int dmc_info[20] = {
-    1 /*abi*/, (int)sizeof(real), NQ, NV, NU, NBODY, NOBS, NSENSORDATA,
-    (WS_WORDS > 0 ? WS_WORDS : 1) /*workspace reals per env*/, TASK, NCON_MAX, NEFC_MAX,
-    INTEGRATOR, NPAIR, LANES/TEAM /*envs per workgroup of dmc_step/dmc_observe (= its
-                                threads unless a team of lanes shares an env);
-                                the workspace is sized for the batch rounded up to this*/,
-    DMC_ENV_MAJOR /*0: state fields are [k][env]*/, NTASKDATA,
-    LANES /*threads per workgroup*/, DMC_NMODELPARAM /*rows of the model-parameter block*/,
-    TEAMED ? 0 : 1 /*dmc_step runs DmcArgs.nsteps control steps per launch*/};
+// self-description read by dmc_api.cpp through hipModuleGetGlobal (dmc_args.h)
+extern "C" __device__ const DmcInfo dmc_info = {
+    .abi = 1, .real_size = (int)sizeof(real), .nq = NQ, .nv = NV, .nu = NU, .nbody = NBODY,
+    .nobs = NOBS, .nsensordata = NSENSORDATA, .ws_per_env = WS_WORDS > 0 ? WS_WORDS : 1,
+    .task = TASK, .ncon_max = NCON_MAX, .nefc_max = NEFC_MAX, .integrator = INTEGRATOR,
+    .npair = NPAIR,
+    .envs_per_block = LANES/TEAM,   // (= its threads unless a team of lanes shares an env)
+    .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA, .threads_per_block = LANES,
+    .nmodelparam = DMC_NMODELPARAM, .seq_launch = TEAMED ? 0 : 1};
 #endif

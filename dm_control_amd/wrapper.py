@@ -20,11 +20,31 @@ ENV_DMC_HIP_LIB = 'DMC_HIP_LIB'
 _DEFAULT_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                             'csrc', 'libdmc_hip.so')
 
-# enum dmc_field
-(FIELD_QPOS, FIELD_QVEL, FIELD_WARMSTART, FIELD_TIME, FIELD_CTRL, FIELD_OBS,
- FIELD_REWARD, FIELD_SENSORDATA, FIELD_XPOS, FIELD_XMAT, FIELD_QACC,
- FIELD_WARN, FIELD_STATS, FIELD_RETURN, FIELD_TASKDATA,
- FIELD_MODELPARAM) = range(16)
+# enum dmc_field, in the header's order: (name, the ModelInfo member that counts
+# the rows or None, rows per count, an empty count still has one row, element
+# kind, agent layout [nenv][k]).  FIELD_<name> is the row's index.
+FIELDS = (
+    ('QPOS', 'nq', 1, True, 'real', False),
+    ('QVEL', 'nv', 1, True, 'real', False),
+    ('WARMSTART', 'nv', 1, True, 'real', False),
+    ('TIME', None, 1, False, 'real', False),
+    ('CTRL', 'nu', 1, True, 'real', False),
+    ('OBS', 'nobs', 1, True, 'real', True),
+    ('REWARD', None, 1, False, 'real', False),
+    ('SENSORDATA', 'nsensordata', 1, True, 'real', False),
+    ('XPOS', 'nbody', 3, False, 'real', False),
+    ('XMAT', 'nbody', 9, False, 'real', False),
+    ('QACC', 'nv', 1, True, 'real', False),
+    ('WARN', None, 1, False, 'uint32', False),
+    ('STATS', None, 3, False, 'int32', False),
+    ('RETURN', None, 1, False, 'real', False),
+    ('TASKDATA', 'ntaskdata', 1, True, 'real', False),
+    ('MODELPARAM', 'nmodelparam', 1, True, 'real', False),
+)
+globals().update(('FIELD_' + f[0], k) for k, f in enumerate(FIELDS))
+
+# bits of `want_outputs` (DMC_STEP_* of the header)
+STEP_OUTPUTS, STEP_STALE_FIRST = 1, 2
 
 
 class Error(Exception):
@@ -197,24 +217,17 @@ class HipBatch:
 
   # -- shapes ---------------------------------------------------------------
   def _shape(self, field):
-    i, n = self.model.info, self.nenv
-    return {
-        FIELD_QPOS: (max(i.nq, 1), n), FIELD_QVEL: (max(i.nv, 1), n),
-        FIELD_WARMSTART: (max(i.nv, 1), n), FIELD_TIME: (n,),
-        FIELD_CTRL: (max(i.nu, 1), n), FIELD_OBS: (n, max(i.nobs, 1)),
-        FIELD_REWARD: (n,), FIELD_SENSORDATA: (max(i.nsensordata, 1), n),
-        FIELD_XPOS: (i.nbody*3, n), FIELD_XMAT: (i.nbody*9, n),
-        FIELD_QACC: (max(i.nv, 1), n), FIELD_WARN: (n,), FIELD_STATS: (3, n),
-        FIELD_RETURN: (n,), FIELD_TASKDATA: (max(i.ntaskdata, 1), n),
-        FIELD_MODELPARAM: (max(i.nmodelparam, 1), n),
-    }[field]
+    _, count, mult, pad, _, agent = FIELDS[field]
+    if count is None and mult == 1:
+      return (self.nenv,)
+    rows = mult
+    if count is not None:
+      rows *= max(getattr(self.model.info, count), int(pad))
+    return (self.nenv, rows) if agent else (rows, self.nenv)
 
   def _dtype(self, field):
-    if field == FIELD_WARN:
-      return np.uint32
-    if field == FIELD_STATS:
-      return np.int32
-    return self.model.dtype
+    kind = FIELDS[field][4]
+    return self.model.dtype if kind == 'real' else np.dtype(kind).type
 
   def read(self, field):
     """Device -> host copy of a whole field, native [k][env] layout."""
@@ -275,7 +288,8 @@ class HipBatch:
 
     stale_first: DMC_STEP_STALE_FIRST (the first substep takes its acceleration
     from the reset state; the reference cheetah's first settle step)."""
-    want_outputs = int(bool(want_outputs)) | (2 if stale_first else 0)
+    want_outputs = ((STEP_OUTPUTS if want_outputs else 0) |
+                    (STEP_STALE_FIRST if stale_first else 0))
     if ctrl is None:
       _check(self._lib.dmc_batch_step(self.ptr, None, 0, 0, 0, nsub,
                                       want_outputs))
