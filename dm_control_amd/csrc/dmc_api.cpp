@@ -434,7 +434,9 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   b->stream = b->own_stream;
   for (int f = 0; f < DMC_FIELD_COUNT && err == hipSuccess; f++) {
     err = hipMalloc(&b->field[f], b->bytes[f]);
-    if (err == hipSuccess) err = hipMemset(b->field[f], 0, b->bytes[f]);
+    // on the batch's stream: it does not wait for the null stream (non-blocking),
+    // so a hipMemset there could land after the launches below and after later writes
+    if (err == hipSuccess) err = hipMemsetAsync(b->field[f], 0, b->bytes[f], b->stream);
   }
   // workspace: ws_per_env reals per env, laid out for the batch rounded up to
   // whole 64-env workgroups (surplus lanes of the last workgroup own a slot)
@@ -442,7 +444,7 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   if (err == hipSuccess)
     err = hipMalloc(&b->ws, atleast1(i.ws_per_env)*npad*rs);
   if (err == hipSuccess)
-    err = hipMemset(b->ws, 0, atleast1(i.ws_per_env)*npad*rs);
+    err = hipMemsetAsync(b->ws, 0, atleast1(i.ws_per_env)*npad*rs, b->stream);
   if (err == hipSuccess) err = hipEventCreate(&b->ev0);
   if (err == hipSuccess) err = hipEventCreate(&b->ev1);
   if (err != hipSuccess) {

@@ -4,6 +4,12 @@
 // with the oracle).  TEST INFRASTRUCTURE ONLY.
 //   stdin: <steps> <nsub>, then per env: <model-parameter block> <qpos> <qvel> <ctrl>
 //   stdout: STEP <t> <env> <qpos> <qvel> | <ncon> <nefc> <iters> <warn>
+// `harness init`: one launch of dmc_init_episode over a batch of any size, every
+// field in a heap block of its own of exactly the unpadded size, pre-filled with
+// INIT_SENTINEL (tests/shim_runner.py compares with tests/device_init_model.py).
+//   stdin: <nenv> <seed> <flags> <task_param_i> [per env: <ncon> for the stats column]
+//   stdout: INIT <env> <qpos> | <qvel> | <warm> | <ctrl> | <time> | <return> |
+//           <taskdata> | <model-parameter block>
 #include "shim.h"
 #include <cstdio>
 #include <cstdlib>
@@ -30,7 +36,65 @@ static void* lane_main(void* arg) {
   return nullptr;
 }
 
-int main() {
+// --------------------------------------------------------------------------
+// init mode
+// --------------------------------------------------------------------------
+constexpr double INIT_SENTINEL = -777.25;
+// the layout of a 2-D field as DESIGN.md 2 states it, not through the kernel's sidx
+static size_t init_at(int k, int e, int n, int K) {
+  return DMC_ENV_MAJOR ? (size_t)e*K + k : (size_t)k*n + e;
+}
+static real* init_field(size_t words) {
+  real* p = new real[words];       // exactly `words`: one past the end is a report
+  for (size_t i = 0; i < words; i++) p[i] = (real)INIT_SENTINEL;
+  return p;
+}
+static void init_print(const real* p, int K, int e, int n, const char* sep) {
+  for (int k = 0; k < K; k++)
+    printf(" %.17g", (double)p[init_at(k, e, n, K > 0 ? K : 1)]);
+  printf("%s", sep);
+}
+
+static int init_main() {
+  int n, flags, param;
+  unsigned long long seed;
+  if (scanf("%d %llu %d %d", &n, &seed, &flags, &param) != 4 || n < 1) {
+    fprintf(stderr, "expected <nenv> <seed> <flags> <task_param_i>\n");
+    return 2;
+  }
+  int* stats = new int[3*(size_t)n];
+  for (int i = 0; i < 3*n; i++) stats[i] = 0;
+  for (int e = 0, ncon; e < n && scanf("%d", &ncon) == 1; e++) stats[init_at(0, e, n, 3)] = ncon;
+  DmcArgs a;
+  memset(&a, 0, sizeof a);
+  a.nenv = n; a.nsub = 1; a.flags = flags; a.task_param_i = param; a.seed = seed;
+  a.qpos = init_field((size_t)NQX*n); a.qvel = init_field((size_t)NVX*n);
+  a.warm = init_field((size_t)NVX*n); a.ctrl_store = init_field((size_t)NUX*n);
+  a.time = init_field(n); a.episode_return = init_field(n);
+  a.taskdata = init_field((size_t)NTDX*n);
+  if (NMP > 0) a.modelparam = init_field((size_t)NMP*n);
+  a.stats = stats;
+  // one env per lane of 64-lane workgroups; the kernel has no barrier, so the
+  // lanes run one after the other on this thread
+  for (int b = 0; b < (n + 63)/64; b++)
+    for (int t = 0; t < 64; t++) {
+      blockIdx.x = (unsigned)b; threadIdx.x = (unsigned)t;
+      dmc_init_episode(a);
+    }
+  for (int e = 0; e < n; e++) {
+    printf("INIT %d", e);
+    init_print(a.qpos, NQ, e, n, " |"); init_print(a.qvel, NV, e, n, " |");
+    init_print(a.warm, NV, e, n, " |"); init_print(a.ctrl_store, NU, e, n, " |");
+    init_print(a.time + e, 1, 0, 1, " |"); init_print(a.episode_return + e, 1, 0, 1, " |");
+    init_print(a.taskdata, NTASKDATA, e, n, " |");
+    if (NMP > 0) init_print(a.modelparam, NMP, e, n, "");
+    printf("\n");
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "init")) return init_main();
   const int n = HARNESS_ENVS;
   const int nq = NQ > 0 ? NQ : 1, nv = NV > 0 ? NV : 1, nu = NU > 0 ? NU : 1;
   std::vector<real> qpos(nq*n), qvel(nv*n), warm(nv*n, 0), tm(n, 0), ctrl(nu*n),

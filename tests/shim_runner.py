@@ -109,6 +109,68 @@ def run(exe, steps, qpos, qvel, ctrl, blocks=None, timeout=600):
   return rows
 
 
+INIT_SENTINEL = -777.25      # what harness.cpp's init mode fills every field with
+INIT_FIELDS = ('qpos', 'qvel', 'warm', 'ctrl', 'time', 'episode_return', 'taskdata',
+               'modelparam')
+
+
+def run_init(exe, nenv, seed, flags=0, task_param_i=0, ncon=None, timeout=300):
+  """One launch of dmc_init_episode over `nenv` envs in a program made by
+  `build` (its init mode: every field a heap block of exactly its size, filled
+  with INIT_SENTINEL).  ncon [nenv]: the contact counts planted in the stats
+  field.  Returns {field: [nenv, k]} as printed -- 17
+  significant digits, so every value is the word the kernel wrote, exactly."""
+  text = '%d %d %d %d\n' % (nenv, int(seed) & (2**64 - 1), flags, task_param_i)
+  if ncon is not None:
+    text += ' '.join('%d' % c for c in ncon) + '\n'
+  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
+  out = subprocess.run([exe, 'init'], input=text, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       universal_newlines=True, env=env, timeout=timeout)
+  assert out.returncode == 0, out.stderr[-3000:]
+  rows = [line.split('|') for line in out.stdout.splitlines() if line.startswith('INIT')]
+  assert [int(r[0].split()[1]) for r in rows] == list(range(nenv))
+  fields = {}
+  for i, name in enumerate(INIT_FIELDS):
+    cols = [r[i].split()[2 if i == 0 else 0:] for r in rows]
+    fields[name] = np.array([[float(x) for x in c] for c in cols]).reshape(nenv, -1)
+  return fields
+
+
+def compare_init(got, want, real_size, fields=INIT_FIELDS):
+  """`got` of `run_init` (or of a device, same shapes) against a
+  `device_init_model.Draw`: the envs the launch writes within the model's
+  tolerance of each value (exact ones: the model rounded to `real`), everything
+  else still `got['before']` (default: the sentinel) bit for bit.  Returns the
+  largest error of a value whose bound is measured, not derived, per class of
+  device_init_model.CPU_ROUNDING_FIGURE and in its unit, eps(real)*scale."""
+  import device_init_model
+  real = np.float32 if real_size == 4 else np.float64
+  before = got.get('before', {})
+  w = want.written
+  figure = {kind: 0.0 for kind in device_init_model.KINDS}
+  for name in fields:
+    g = got[name]
+    b = before.get(name, np.full(g.shape, INIT_SENTINEL))
+    ref = getattr(want, name)
+    if ref is None:           # a field this launch leaves alone
+      np.testing.assert_array_equal(g, b, err_msg=name)
+      continue
+    ref = np.asarray(ref, np.float64).reshape(len(w), -1)
+    np.testing.assert_array_equal(g[~w], b[~w], err_msg=name + ' of envs not drawn')
+    tol = np.broadcast_to(device_init_model.atol(want, name, real_size), ref.shape)[w]
+    rounded = ref[w].astype(real).astype(np.float64)
+    np.testing.assert_array_equal(g[w][tol == 0], rounded[tol == 0], err_msg=name + ' (exact values)')
+    err = np.abs(g[w] - ref[w])[tol > 0]
+    assert np.all(err <= tol[tol > 0]), (name, float((err/tol[tol > 0]).max()))
+    for kind in device_init_model.KINDS:
+      scale = np.broadcast_to(device_init_model.scales(want, kind).get(name, np.zeros(1)),
+                              ref.shape)[w]
+      if w.any() and (scale > 0).any():
+        figure[kind] = max(figure[kind], float((np.abs(g[w] - ref[w])[scale > 0]/
+                                                (np.finfo(real).eps*scale[scale > 0])).max()))
+  return figure
+
+
 def oracle_at(model, qpos, qvel, ctrl):
   d = oracle.OracleData(oracle.OracleModel(model))
   d.qpos[:] = qpos

@@ -13,7 +13,9 @@ oracle are tests/shim_runner.py; the tests here pass no control (zeros).
 import numpy as np
 import pytest
 
+import device_init_model as dim
 import helpers
+import kat_models
 import shim_runner
 from dm_control_amd.mjcf import compiler
 
@@ -172,3 +174,120 @@ def test_team_build_of_a_scene_with_several_trees(name, sanitizer, team, steps, 
 
   shim_runner.compare(rows, [m], qpos[None], qvel[None], ctrl, steps, before_step=rows_across_trees)
   assert any(coupled), 'no constraint row touched two trees: the scene does not test the coupling'
+
+
+# ---------------------------------------------------------------------------
+# dmc_init_episode (the harness's init mode): every field in a heap block of
+# exactly nenv envs, compared value by value with tests/device_init_model.py
+# ---------------------------------------------------------------------------
+INIT_SHAPES = (1, 61, 67, 130)      # one lane; short of, past and two past a 64-lane workgroup
+# (domain, poles, lanes per env or None): the one-lane source keeps [k][env],
+# the several-lanes source [env][k]
+INIT_BUILDS = [(domain, poles, None) for domain, poles in sorted(
+    set((c[1], c[2]) for c in dim.CASES if c[1] != 'humanoid'), key=str)] + [
+        ('humanoid', None, 64), ('walker', None, 64), ('point_mass', None, 64)]
+
+
+@pytest.fixture(scope='module')
+def init_exe(tmp_path_factory):
+  """build(...) of the harness once per (domain, poles, group, f64, per_env)."""
+  made = {}
+
+  def get(domain, poles, group, f64, per_env=()):
+    key = (domain, poles, group, f64, per_env)
+    if key not in made:
+      model = dim.case_model(domain, poles)
+      made[key] = (model, shim_runner.build(
+          model, helpers.TASKS[domain], tmp_path_factory.mktemp('init'), group=group, f64=f64,
+          per_env=per_env))
+    return made[key]
+  return get
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('f64', [True, False], ids=['f64', 'f32'])
+@pytest.mark.parametrize('domain,poles,group', INIT_BUILDS)
+def test_init_kernel_is_clean_and_draws_the_model(domain, poles, group, f64, init_exe):
+  """Every recipe branch of the domain, four batch sizes, a small seed and one
+  of the product's form: clean under ASan + UBSan with buffers of exactly nenv
+  envs (a missing `e >= nenv` guard or a wrong stride is a report), and every
+  value the model's."""
+  model, exe = init_exe(domain, poles, group, f64)
+  lines = [c for c in dim.CASES if (c[1], c[2]) == (domain, poles)]
+  assert lines
+  for _, _, _, param in lines:
+    for nenv in INIT_SHAPES:
+      for seed in dim.SEEDS:
+        got = shim_runner.run_init(exe, nenv, seed, 0, param)
+        want = dim.draw(model, helpers.TASKS[domain], param, seed, nenv)
+        shim_runner.compare_init(got, want, 8 if f64 else 4)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('f64', [True, False], ids=['f64', 'f32'])
+def test_init_kernel_of_a_model_without_a_task_resets_only(f64, tmp_path):
+  """Task id 0 (TASK_NONE: a known-answer model with three free joints): no
+  recipe applies, so a launch without flags draws nothing -- qpos0, zeros."""
+  model = compiler.from_xml_string(kat_models.PRIMITIVES)
+  exe = shim_runner.build(model, 0, tmp_path, f64=f64)
+  for nenv in INIT_SHAPES:
+    got = shim_runner.run_init(exe, nenv, dim.SEEDS[1], 0, 0)
+    want = dim.draw(model, 0, 0, dim.SEEDS[1], nenv)
+    assert not want.draws.any() and want.taskdata is None
+    shim_runner.compare_init(got, want, 8 if f64 else 4)
+    real = np.float64 if f64 else np.float32
+    np.testing.assert_array_equal(got['qpos'], np.tile(model.qpos0.astype(real), (nenv, 1)))
+    assert np.ptp(model.qpos0) > 0
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('domain,group,f64,param', [
+    ('humanoid', 64, False, 0), ('point_mass', None, True, 1), ('reacher', None, False, 0)])
+def test_init_kernel_only_colliding_leaves_clean_envs_alone(domain, group, f64, param, init_exe):
+  model, exe = init_exe(domain, None, group, f64)
+  for nenv in (67, 130):
+    ncon = np.random.RandomState(nenv).randint(0, 3, nenv)*(np.arange(nenv) % 3 != 1)
+    ncon[-1] = 4                      # the last env of the short workgroup redraws
+    assert (ncon == 0).sum() > nenv//3 and (ncon > 0).sum() > nenv//4
+    got = shim_runner.run_init(exe, nenv, dim.SEED_ONLY_COLLIDING, dim.FLAG_ONLY_COLLIDING,
+                               param, ncon=ncon)
+    want = dim.draw(model, helpers.TASKS[domain], param, dim.SEED_ONLY_COLLIDING, nenv,
+                    dim.FLAG_ONLY_COLLIDING, stats_ncon=ncon)
+    np.testing.assert_array_equal(want.written, ncon > 0)
+    # envs at ncon 0 keep every sentinel bit; the others are the draw of the new seed
+    shim_runner.compare_init(got, want, 8 if f64 else 4)
+    assert (got['qpos'][ncon == 0] == shim_runner.INIT_SENTINEL).all()
+    assert (got['qpos'][ncon > 0] != shim_runner.INIT_SENTINEL).all()
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('domain,group,f64,param', [
+    ('humanoid', 64, True, 0), ('point_mass', None, False, 1), ('reacher', None, True, 0)])
+def test_init_kernel_reset_only_is_mj_reset_data(domain, group, f64, param, init_exe):
+  model, exe = init_exe(domain, None, group, f64)
+  for nenv in (1, 67):
+    got = shim_runner.run_init(exe, nenv, dim.SEEDS[1], dim.FLAG_RESET_ONLY, param)
+    want = dim.draw(model, helpers.TASKS[domain], param, dim.SEEDS[1], nenv, dim.FLAG_RESET_ONLY)
+    assert want.taskdata is None and want.modelparam is None      # left alone: still the sentinel
+    shim_runner.compare_init(got, want, 8 if f64 else 4)
+    real = np.float64 if f64 else np.float32
+    np.testing.assert_array_equal(got['qpos'], np.tile(model.qpos0.astype(real), (nenv, 1)))
+    assert not got['qvel'].any() and not got['warm'].any() and not got['time'].any()
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize('domain,group,f64', [('point_mass', None, True), ('walker', 64, False)])
+def test_init_kernel_batch_creation_writes_the_compiled_defaults(domain, group, f64, init_exe):
+  """RESET_ONLY | TASKDATA_DEFAULT on a build with per-env fields: the task data
+  at the model's values and the model-parameter block that
+  `dm_control_amd.model_params` computes for the nominal model, in every env."""
+  per_env = ('body_mass', 'geom_friction')
+  model, exe = init_exe(domain, None, group, f64, per_env)
+  flags = dim.FLAG_RESET_ONLY | dim.FLAG_TASKDATA_DEFAULT
+  for nenv in (1, 67, 130):
+    got = shim_runner.run_init(exe, nenv, 0, flags, 1)
+    want = dim.draw(model, helpers.TASKS[domain], 1, 0, nenv, flags, per_env=per_env)
+    assert want.modelparam.shape[1] > model.nbody and np.ptp(want.modelparam, axis=0).max() == 0
+    shim_runner.compare_init(got, want, 8 if f64 else 4)
+    if domain == 'point_mass':
+      assert np.abs(got['taskdata']).max() > 0
