@@ -24,6 +24,8 @@
 #include <vector>
 
 #include "dmc_args.h"
+static_assert(DMC_EP_DONE_LIMIT == DMC_DONE_LIMIT && DMC_EP_DONE_BAD_STATE == DMC_DONE_BAD_STATE,
+              "the done bits of the header are the kernels'");
 
 namespace {
 
@@ -55,6 +57,7 @@ struct dmc_model {
   hipModule_t module = nullptr;
   hipFunction_t k_step = nullptr, k_observe = nullptr, k_init = nullptr;
   dmc_model_info info{};
+  int episode_caps = 0;   // DMC_FLAG_* bits of the code object's dmc_episode_caps (0: it has none)
 };
 
 struct dmc_batch {
@@ -72,6 +75,11 @@ struct dmc_batch {
   int task_param_i = 0;
   bool aux_outputs = false;
   double task_param_r[4] = {0, 0, 0, 0};
+  // per-env episodes: device int32[nenv] arrays indexed by dmc_episode_array
+  int* episode[DMC_EPISODE_COUNT] = {};
+  bool episodes = false;   // init and output-producing steps carry DMC_FLAG_EPISODES
+  bool masked = false;     // init, forward and step carry DMC_FLAG_MASKED
+  int step_limit = 0;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false;
@@ -179,14 +187,46 @@ void fill_args(dmc_batch* b, DmcArgs& a) {
   a.warn = (unsigned*)b->field[DMC_FIELD_WARN];
   a.stats = (int*)b->field[DMC_FIELD_STATS];
   a.ws = b->ws;
+  a.env_mask = b->episode[DMC_EPISODE_MASK];
+  a.ep_step = b->episode[DMC_EPISODE_STEP];
+  a.ep_done = b->episode[DMC_EPISODE_DONE];
+  a.step_limit = b->step_limit;
+  if (b->masked) a.flags |= DMC_FLAG_MASKED;   // (callers OR their own bits into `flags`)
+}
+
+// the episode block: allocated (and zeroed, on the batch's stream) on first use
+int episode_block(dmc_batch* b, const char* who) {
+  const int need = DMC_FLAG_MASKED | DMC_FLAG_EPISODES | DMC_FLAG_ZERO_TIME;
+  if ((b->model->episode_caps & need) != need)
+    return fail("%s: this code object does not take an env mask or per-env episodes "
+                "(a team-mode build, or one built before version 103)", who);
+  if (b->episode[0]) return 0;
+  HIP_TRY(hipSetDevice(b->model->device));
+  const size_t bytes = (size_t)b->nenv*sizeof(int);
+  for (int k = 0; k < DMC_EPISODE_COUNT; k++) {
+    HIP_TRY(hipMalloc((void**)&b->episode[k], bytes));
+    HIP_TRY(hipMemsetAsync(b->episode[k], 0, bytes, b->stream));
+  }
+  return 0;
+}
+
+int episode_array(const dmc_batch* b, int which, size_t bytes, const char* who) {
+  if (which < 0 || which >= DMC_EPISODE_COUNT) return fail("%s: unknown array %d", who, which);
+  if (!b->episode[0]) return fail("%s: the batch has no episode block "
+                                  "(dmc_batch_episodes_enable)", who);
+  if (bytes != (size_t)b->nenv*sizeof(int))
+    return fail("%s: the array has %zu bytes, caller passed %zu", who,
+                (size_t)b->nenv*sizeof(int), bytes);
+  return 0;
 }
 
 }  // namespace
 
 extern "C" {
 
-// 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM; 102: dmc_model_info.seq_launch
-int dmc_version(void) { return 102; }
+// 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM; 102: dmc_model_info.seq_launch;
+// 103: per-env episodes (dmc_batch_episodes_enable and what follows it in the header)
+int dmc_version(void) { return 103; }
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -391,6 +431,13 @@ int load_model(const char* path, const void* image, int device_id, dmc_model** o
   i.env_major = d.env_major != 0;
   i.nmodelparam = d.nmodelparam > 0 ? d.nmodelparam : 0;
   i.seq_launch = d.seq_launch == 1;
+  DmcEpisodeCaps caps = 0;
+  if (hipModuleGetGlobal(&dptr, &bytes, m->module, "dmc_episode_caps") == hipSuccess &&
+      bytes >= sizeof caps &&
+      hipMemcpy(&caps, dptr, sizeof caps, hipMemcpyDeviceToHost) == hipSuccess)
+    m->episode_caps = caps;
+  else
+    (void)hipGetLastError();   // an older code object: the episode entry points refuse it
   *out = m;
   return 0;
 }
@@ -456,7 +503,7 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   {   // per-instance task data and model parameters start from the compiled model's values
     DmcArgs a;
     fill_args(b, a);
-    a.flags = DMC_FLAG_RESET_ONLY | DMC_FLAG_TASKDATA_DEFAULT;
+    a.flags |= DMC_FLAG_RESET_ONLY | DMC_FLAG_TASKDATA_DEFAULT;
     if (launch(b, model->k_init, a, TASK_SETUP)) return -1;
   }
   return dmc_batch_reset(b);
@@ -469,6 +516,8 @@ void dmc_batch_free(dmc_batch* b) {
     if (b->field[f]) (void)hipFree(b->field[f]);
   if (b->ws) (void)hipFree(b->ws);
   if (b->ctrl_staging) (void)hipFree(b->ctrl_staging);
+  for (int k = 0; k < DMC_EPISODE_COUNT; k++)
+    if (b->episode[k]) (void)hipFree(b->episode[k]);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -499,7 +548,9 @@ int dmc_batch_reset(dmc_batch* b) {
   // masked off via DMC_FLAG_RESET_ONLY.
   DmcArgs a;
   fill_args(b, a);
-  a.flags = DMC_FLAG_RESET_ONLY;
+  // (the whole batch, whatever dmc_batch_set_masked says; with episodes enabled
+  // every env's step count and done bits restart with its state)
+  a.flags = DMC_FLAG_RESET_ONLY | (b->episodes ? DMC_FLAG_EPISODES : 0);
   if (launch(b, b->model->k_init, a, TASK_SETUP)) return -1;
   HIP_TRY(hipMemsetAsync(b->field[DMC_FIELD_WARN], 0, b->bytes[DMC_FIELD_WARN],
                          b->stream));
@@ -559,7 +610,8 @@ int dmc_batch_init_episode(dmc_batch* b, uint64_t seed, int only_colliding) {
   DmcArgs a;
   fill_args(b, a);
   a.seed = seed;
-  a.flags = only_colliding ? DMC_FLAG_ONLY_COLLIDING : 0;
+  a.flags |= (only_colliding ? DMC_FLAG_ONLY_COLLIDING : 0) |
+             (b->episodes ? DMC_FLAG_EPISODES : 0);
   return launch(b, b->model->k_init, a, TASK_SETUP);
 }
 
@@ -568,7 +620,7 @@ int dmc_batch_forward(dmc_batch* b, int count_contacts) {
   HIP_TRY(hipSetDevice(b->model->device));
   DmcArgs a;
   fill_args(b, a);
-  a.flags = count_contacts ? DMC_FLAG_COUNT_CONTACTS : 0;
+  a.flags |= count_contacts ? DMC_FLAG_COUNT_CONTACTS : 0;
   return launch(b, b->model->k_observe, a, MODEL_SHAPED);
 }
 
@@ -586,8 +638,15 @@ int step_launch(dmc_batch* b, const void* ctrl, long long stride_k,
   DmcArgs a;
   fill_args(b, a);
   a.nsub = nsub;
-  a.flags = (want_outputs & DMC_STEP_OUTPUTS) ? 0 : DMC_FLAG_NO_OUTPUT;
+  a.flags |= (want_outputs & DMC_STEP_OUTPUTS) ? (b->episodes ? DMC_FLAG_EPISODES : 0)
+                                               : DMC_FLAG_NO_OUTPUT;
   if (want_outputs & DMC_STEP_STALE_FIRST) a.flags |= DMC_FLAG_STALE_FIRST;
+  if (want_outputs & DMC_STEP_ZERO_TIME) {
+    if (!(b->model->episode_caps & DMC_FLAG_ZERO_TIME))
+      return fail("dmc_batch_step: this code object does not take DMC_STEP_ZERO_TIME "
+                  "(a team-mode build, or one built before version 103)");
+    a.flags |= DMC_FLAG_ZERO_TIME;
+  }
   if (ctrl && i.nu > 0) {
     a.flags |= DMC_FLAG_CTRL;
     if (on_device) {
@@ -640,7 +699,8 @@ int dmc_batch_step_n(dmc_batch* b, const void* ctrl, long long stride_k,
   // One launch per chunk of control steps where the code object loops over them
   // itself (bounded, so that no launch occupies a shared device for long), else
   // one launch per step.  DMC_STEP_STALE_FIRST is about the sequence's first step.
-  const int chunk_max = b->model->info.seq_launch ? DMC_SEQ_LAUNCH_MAX_STEPS : 1;
+  // (with per-env episodes every control step is a launch: an env freezes between steps)
+  const int chunk_max = b->model->info.seq_launch && !b->episodes ? DMC_SEQ_LAUNCH_MAX_STEPS : 1;
   for (int t = 0; t < nsteps;) {
     const int chunk = nsteps - t < chunk_max ? nsteps - t : chunk_max;
     if (step_launch(b, (const char*)ctrl + (long long)t*stride_t*rs, stride_k, stride_env,
@@ -701,10 +761,66 @@ int dmc_batch_copy_state(dmc_batch* dst, const dmc_batch* src) {
   for (int f = 0; f < DMC_FIELD_COUNT; f++)
     HIP_TRY(hipMemcpyAsync(dst->field[f], src->field[f], dst->bytes[f],
                            hipMemcpyDeviceToDevice, dst->stream));
+  if (src->episode[0]) {
+    if (episode_block(dst, "dmc_batch_copy_state")) return -1;
+    for (int k = 0; k < DMC_EPISODE_COUNT; k++)
+      HIP_TRY(hipMemcpyAsync(dst->episode[k], src->episode[k], (size_t)dst->nenv*sizeof(int),
+                             hipMemcpyDeviceToDevice, dst->stream));
+    dst->episodes = src->episodes;
+    dst->step_limit = src->step_limit;
+  }
   dst->task_param_i = src->task_param_i;
   dst->aux_outputs = src->aux_outputs;
   memcpy(dst->task_param_r, src->task_param_r, sizeof dst->task_param_r);
   HIP_TRY(hipStreamSynchronize(dst->stream));
+  return 0;
+}
+
+int dmc_batch_episodes_enable(dmc_batch* b, int step_limit) {
+  if (!b) return fail("null batch");
+  if (episode_block(b, "dmc_batch_episodes_enable")) return -1;
+  b->episodes = true;
+  b->step_limit = step_limit;
+  return 0;
+}
+
+void* dmc_batch_episode_ptr(dmc_batch* b, int which) {
+  if (!b || which < 0 || which >= DMC_EPISODE_COUNT) return nullptr;
+  return b->episode[which];
+}
+
+int dmc_batch_episode_read(dmc_batch* b, int which, int* dst, size_t bytes) {
+  if (!b || !dst) return fail("dmc_batch_episode_read: null argument");
+  if (episode_array(b, which, bytes, "dmc_batch_episode_read")) return -1;
+  HIP_TRY(hipSetDevice(b->model->device));
+  HIP_TRY(hipMemcpyAsync(dst, b->episode[which], bytes, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int dmc_batch_episode_write(dmc_batch* b, int which, const int* src, size_t bytes) {
+  if (!b || !src) return fail("dmc_batch_episode_write: null argument");
+  if (episode_array(b, which, bytes, "dmc_batch_episode_write")) return -1;
+  HIP_TRY(hipSetDevice(b->model->device));
+  HIP_TRY(hipMemcpyAsync(b->episode[which], src, bytes, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  return 0;
+}
+
+int dmc_batch_mask_from_done(dmc_batch* b) {
+  if (!b) return fail("null batch");
+  if (episode_array(b, DMC_EPISODE_MASK, (size_t)b->nenv*sizeof(int), "dmc_batch_mask_from_done"))
+    return -1;
+  HIP_TRY(hipSetDevice(b->model->device));
+  HIP_TRY(hipMemcpyAsync(b->episode[DMC_EPISODE_MASK], b->episode[DMC_EPISODE_DONE],
+                         (size_t)b->nenv*sizeof(int), hipMemcpyDeviceToDevice, b->stream));
+  return 0;
+}
+
+int dmc_batch_set_masked(dmc_batch* b, int on) {
+  if (!b) return fail("null batch");
+  if (on && episode_block(b, "dmc_batch_set_masked")) return -1;
+  b->masked = on != 0;
   return 0;
 }
 

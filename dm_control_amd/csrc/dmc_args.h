@@ -37,6 +37,12 @@ struct DmcArgs {
   // ctrl + t*ctrl_st.  A zero-filled block (nsteps 0) is one step.
   int nsteps;
   long long ctrl_st;
+  // per-env episodes (code objects that report the flags in dmc_episode_caps).
+  // A zero-filled block is a launch over the whole batch without bookkeeping.
+  const int* env_mask;     // [nenv] DMC_FLAG_MASKED: the launch touches env e only if env_mask[e] != 0
+  int* ep_step;            // [nenv] DMC_FLAG_EPISODES: control steps of the episode
+  int* ep_done;            // [nenv] DMC_FLAG_EPISODES: DMC_EP_DONE_* bits, nonzero = frozen until re-initialised
+  int step_limit;          // ep_done gets DMC_EP_DONE_LIMIT once ep_step >= step_limit (<= 0: never)
 };
 // bits of DmcArgs.flags
 #define DMC_FLAG_CTRL 1          // ctrl pointer valid (else reuse ctrl_store)
@@ -46,6 +52,13 @@ struct DmcArgs {
 #define DMC_FLAG_RESET_ONLY 16     // dmc_init_episode: mj_resetData only
 #define DMC_FLAG_TASKDATA_DEFAULT 32  // dmc_init_episode: task data and model parameters <- model values
 #define DMC_FLAG_STALE_FIRST 64    // dmc_step: first substep takes its acceleration from the reset state
+#define DMC_FLAG_MASKED 128        // all kernels: envs with env_mask[e] == 0 are left alone, every field bit for bit
+#define DMC_FLAG_EPISODES 256      // dmc_step with outputs: skip envs with ep_done != 0, count ep_step, set ep_done;
+                                   // dmc_init_episode: ep_step, ep_done and warn <- 0 for the envs it writes
+#define DMC_FLAG_ZERO_TIME 512     // dmc_step: store time = 0 for the envs it stepped (settle launches of a reset)
+// bits of ep_done (enum dmc_done_bit of the header)
+#define DMC_EP_DONE_LIMIT 1        // the episode reached step_limit
+#define DMC_EP_DONE_BAD_STATE 2    // a launch raised a warning bit (mjtWarning) for the env
 
 // `dmc_info`: what a code object says about itself, read by dmc_api.cpp through
 // hipModuleGetGlobal.  The member order is the layout in the code object; new
@@ -66,3 +79,9 @@ struct alignas(16) DmcInfo {
   int seq_launch;         // 1: dmc_step runs DmcArgs.nsteps control steps per launch
 };
 static_assert(sizeof(DmcInfo) == 20*sizeof(int), "dmc_info is 20 ints");
+
+// `dmc_episode_caps`: a second device global next to `dmc_info` (whose size is
+// part of the ABI): the DMC_FLAG_* bits of the per-env episode contract that the
+// code object honours.  A code object without the global, or with a bit clear
+// (team mode), makes the host refuse the entry points that need it.
+typedef int DmcEpisodeCaps;

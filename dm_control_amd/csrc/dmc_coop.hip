@@ -1833,6 +1833,7 @@ dmc_step(DmcArgs a) {
   const int slot = DUO ? 0 : threadIdx.x/G;
   const int e = xcd_contiguous(blockIdx.x, (a.nenv + EPB - 1)/EPB)*EPB + slot;
   if (e >= a.nenv) return;               // whole groups (DUO: both waves) leave together
+  if (!env_selected(a, e, counts_episodes(a))) return;   // (the same: every lane of an env reads its words)
   Coop C;
   C.S = coop_lds + slot*ENV_WORDS;
   C.l = threadIdx.x % G;
@@ -1892,7 +1893,9 @@ dmc_step(DmcArgs a) {
     o[3] = (real)(int)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF);
   }
 #endif
+  if (a.flags & DMC_FLAG_ZERO_TIME) C.time = 0;
   C.store(a, e);
+  if (l == 0 && counts_episodes(a)) count_episode_step(a, e, C.warn);
 }
 
 // observation / reward / sensors of the current state (reset, after_reset)
@@ -1902,6 +1905,7 @@ dmc_observe(DmcArgs a) {
   const int slot = DUO ? 0 : threadIdx.x/G;
   const int e = xcd_contiguous(blockIdx.x, (a.nenv + EPB - 1)/EPB)*EPB + slot;
   if (e >= a.nenv) return;
+  if (!env_selected(a, e, false)) return;
   Coop C;
   C.S = coop_lds + slot*ENV_WORDS;
   C.l = threadIdx.x % G;
@@ -1948,3 +1952,4 @@ extern "C" __device__ const DmcInfo dmc_info = {
     .task = TASK, .ncon_max = NCON_MAX, .nefc_max = NEFC_MAX, .integrator = INTEGRATOR,
     .npair = NPAIR, .envs_per_block = EPB, .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA,
     .threads_per_block = NTHREADS, .nmodelparam = DMC_NMODELPARAM, .seq_launch = 0};
+extern "C" __device__ const DmcEpisodeCaps dmc_episode_caps = EPISODE_CAPS;

@@ -357,6 +357,41 @@ enum { TASK_NONE = 0, TASK_CARTPOLE = 1, TASK_CHEETAH = 2, TASK_HUMANOID = 3,
 #define DMC_CREALPTR const real*
 #include "dmc_args.h"
 
+// ---------------------------------------------------------------------------
+// Per-env episodes (dmc_args.h): the flags this code object honours, reported in
+// the device global `dmc_episode_caps`.  Team mode takes none of them: a team
+// build reports 0, the host refuses, and every test below is false at compile time.
+// ---------------------------------------------------------------------------
+constexpr int EPISODE_CAPS =
+    TEAMED ? 0 : (DMC_FLAG_MASKED | DMC_FLAG_EPISODES | DMC_FLAG_ZERO_TIME);
+static_assert(!TEAMED || EPISODE_CAPS == 0, "team mode: no env mask and no per-env episodes");
+// does this launch touch env e?  (dmc_step: `counting` = an output-producing
+// launch with DMC_FLAG_EPISODES, which leaves a finished env frozen)
+DEV bool env_selected(const DmcArgs& a, int e, bool counting) {
+  if (!EPISODE_CAPS) return true;
+  if ((a.flags & DMC_FLAG_MASKED) && a.env_mask[e] == 0) return false;
+  return !(counting && a.ep_done[e] != 0);
+}
+DEV bool counts_episodes(const DmcArgs& a) {
+  return EPISODE_CAPS && (a.flags & DMC_FLAG_EPISODES) && !(a.flags & DMC_FLAG_NO_OUTPUT);
+}
+// after the env's state is stored: one more control step of its episode
+DEV void count_episode_step(const DmcArgs& a, int e, unsigned warn) {
+  const int steps = a.ep_step[e] + 1;
+  a.ep_step[e] = steps;
+  a.ep_done[e] = (a.step_limit > 0 && steps >= a.step_limit ? DMC_EP_DONE_LIMIT : 0) |
+                 (warn ? DMC_EP_DONE_BAD_STATE : 0);
+}
+// The lanes of the workgroup (one wavefront: LANES == 64) for which `p` holds, as
+// a bit per lane.  Lanes past the batch have left before.  The host shim runs one
+// lane per program unless its harness brings a ballot over its threads.
+#if !defined(DMC_HOST_SHIM)
+DEV unsigned long long block_ballot(bool p) { return __ballot(p); }
+#elif !defined(DMC_SHIM_BLOCK_BALLOT)
+DEV unsigned long long block_ballot(bool p) { return (unsigned long long)p << threadIdx.x; }
+#endif
+constexpr unsigned long long ALL_LANES = ~0ULL;
+
 // Layout of the 2-D state fields in HBM.  One env per lane: [k][env], so a
 // wave's loads are unit-stride over envs.  One env per group of lanes
 // (dmc_coop.hip): [env][k], so a group's loads are unit-stride over k -- with
@@ -4698,8 +4733,10 @@ constexpr bool OBS_STAGE_FITS = !TEAMED && LDS_WORDS >= LANES*(NOBS > 0 ? NOBS :
 
 // hands over what the task layer computed for the state in E: observation,
 // reward, sensors, aux frames, stats (not the episode return)
+// `live`: the lanes of the workgroup that are still here (ALL_LANES: every lane
+// with an env, the launch masks none out)
 DEV void write_outputs(const Env& E, const DmcArgs& a, int e, const real* obs, real rew,
-                       real* lds_base) {
+                       real* lds_base, unsigned long long live) {
   const long long n = a.nenv;
   if (OBS_STAGE_FITS && a.obs_sk == 1 && a.obs_se == NOBS) {
     const int lane = threadIdx.x;
@@ -4710,9 +4747,18 @@ DEV void write_outputs(const Env& E, const DmcArgs& a, int e, const real* obs, r
     const long long left = n - base;
     const int nvalid = left < (long long)blockDim.x ? (int)left : (int)blockDim.x;
     real* out = a.obs + base*NOBS;
-    // lanes 0..nvalid-1 are exactly the active ones of a partial last block
-    for (int w = lane; w < nvalid*NOBS; w += nvalid)
-      out[w] = lds_base[(w % NOBS)*LANES + w/NOBS];
+    if (live == ALL_LANES) {
+      // lanes 0..nvalid-1 are exactly the active ones of a partial last block
+      for (int w = lane; w < nvalid*NOBS; w += nvalid)
+        out[w] = lds_base[(w % NOBS)*LANES + w/NOBS];
+    } else {
+      // a masked launch: the lanes left share the words of the rows of their envs
+      // (the column of a lane that left was never written, its row stays as it is)
+      const int rank = __builtin_popcountll(live & ((1ULL << lane) - 1));
+      const int nlive = __builtin_popcountll(live);
+      for (int w = rank; w < nvalid*NOBS; w += nlive)
+        if ((live >> (w/NOBS)) & 1) out[w] = lds_base[(w % NOBS)*LANES + w/NOBS];
+    }
   } else {
     DMC_UNROLL
     for (int k = 0; k < NOBS; k++)
@@ -4748,7 +4794,7 @@ DEV void write_outputs(const Env& E, const DmcArgs& a, int e, const real* obs, r
 }
 
 DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
-                       real* lds_base) {
+                       real* lds_base, unsigned long long live = ALL_LANES) {
   const long long n = a.nenv;
   if (TEAMED && TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0) {
     // no task: the observation is the (shared) state, every lane copies its share
@@ -4768,7 +4814,7 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
   real obs[NOBS > 0 ? NOBS : 1];
   const real rew = task_outputs(E, a, obs);
   if (TEAMED && tlane() != 0) return;
-  write_outputs(E, a, e, obs, rew, lds_base);
+  write_outputs(E, a, e, obs, rew, lds_base, live);
   if (accumulate) a.episode_return[e] += rew;
 }
 
@@ -4793,6 +4839,14 @@ extern "C" __global__ void __launch_bounds__(LANES, DMC_WAVES_PER_EU)
 dmc_step(DmcArgs a) {
   const int e = (int)((blockIdx.x*blockDim.x + threadIdx.x)/TEAM);
   if (e >= a.nenv) return;                 // (team mode: a team leaves together)
+  // a masked-out or finished env leaves like the lanes past the batch; the ones
+  // that stay know of each other for the transposed observation store
+  unsigned long long live = ALL_LANES;
+  if (EPISODE_CAPS && ((a.flags & DMC_FLAG_MASKED) || counts_episodes(a))) {
+    const bool stays = env_selected(a, e, counts_episodes(a));
+    live = block_ballot(stays);
+    if (!stays) return;
+  }
   Env E;
   real time;
   const long long n = a.nenv;
@@ -4874,7 +4928,7 @@ dmc_step(DmcArgs a) {
     real obs[NOBS > 0 ? NOBS : 1];
     const real rew = task_outputs(E, a, obs);
     ret += rew;
-    write_outputs(E, a, e, obs, rew, lds_rows);
+    write_outputs(E, a, e, obs, rew, lds_rows, live);
     a.episode_return[e] = ret;
   }
 #ifdef DMC_SOLVER_PROFILE
@@ -4884,7 +4938,9 @@ dmc_step(DmcArgs a) {
 #ifdef DMC_STEP_PROFILE
   if (a.xpos && tlane() == 0) for (int k = 0; k < 8; k++) a.xpos[(long long)k*n + e] = E.prof[k];
 #endif
+  if (EPISODE_CAPS && (a.flags & DMC_FLAG_ZERO_TIME)) time = 0;
   store_env(E, a, e, time);
+  if (counts_episodes(a)) count_episode_step(a, e, E.warn);
 }
 
 // observation / reward / sensors of the current state (reset, after_reset)
@@ -4892,6 +4948,12 @@ extern "C" __global__ void __launch_bounds__(LANES, DMC_WAVES_PER_EU)
 dmc_observe(DmcArgs a) {
   const int e = (int)((blockIdx.x*blockDim.x + threadIdx.x)/TEAM);
   if (e >= a.nenv) return;                 // (team mode: a team leaves together)
+  unsigned long long live = ALL_LANES;
+  if (EPISODE_CAPS && (a.flags & DMC_FLAG_MASKED)) {
+    const bool stays = env_selected(a, e, false);
+    live = block_ballot(stays);
+    if (!stays) return;
+  }
   Env E;
   real time;
   const long long n = a.nenv;
@@ -4919,7 +4981,7 @@ dmc_observe(DmcArgs a) {
     E.ncon = 0; E.nefc = 0; E.nmerged = 0;
     if (NPAIR > 0) detect_contacts(E, W);
   }
-  store_outputs(E, a, e, false, lds_rows);
+  store_outputs(E, a, e, false, lds_rows, live);
   store_env(E, a, e, time);
 }
 
@@ -4952,6 +5014,7 @@ dmc_init_episode(DmcArgs a) {
   const int e = blockIdx.x*blockDim.x + threadIdx.x;   // one env per lane in every build
   if (e >= a.nenv) return;
   const long long n = a.nenv;
+  if (!env_selected(a, e, false)) return;     // (composes with the test below: both must hold)
   if ((a.flags & DMC_FLAG_ONLY_COLLIDING) && a.stats[sidx(0, e, n, 3)] == 0) return;
   Rng rng = {a.seed*0x2545F4914F6CDD1DULL + (uint64_t)e, 0};
   real qpos[NQ > 0 ? NQ : 1], qvel[NVX];
@@ -5039,6 +5102,9 @@ dmc_init_episode(DmcArgs a) {
   for (int i = 0; i < NU; i++) a.ctrl_store[sidx(i, e, n, NUX)] = 0;
   a.time[e] = 0;
   a.episode_return[e] = 0;
+  if (EPISODE_CAPS && (a.flags & DMC_FLAG_EPISODES)) {     // a new episode of this env
+    a.ep_step[e] = 0; a.ep_done[e] = 0; a.warn[e] = 0;
+  }
 }
 
 #ifndef DMC_COOP_BUILD
@@ -5051,4 +5117,5 @@ extern "C" __device__ const DmcInfo dmc_info = {
     .envs_per_block = LANES/TEAM,   // (= its threads unless a team of lanes shares an env)
     .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA, .threads_per_block = LANES,
     .nmodelparam = DMC_NMODELPARAM, .seq_launch = TEAMED ? 0 : 1};
+extern "C" __device__ const DmcEpisodeCaps dmc_episode_caps = EPISODE_CAPS;
 #endif

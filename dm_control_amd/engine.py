@@ -551,8 +551,12 @@ class Physics(_control.Physics):
     """Zero-copy control: a device address plus element strides (in reals)."""
     self._pending_ctrl = ('device', int(ptr), int(stride_k), int(stride_env))
 
-  def step(self, n_sub_steps=1, outputs=True, check=True, stale_first=False):
+  def step(self, n_sub_steps=1, outputs=True, check=True, stale_first=False,
+           zero_time=False):
     """`n_sub_steps` x (mj_step2|mj_step + mj_step1), one kernel launch.
+
+    zero_time: the stepped envs end with time 0 (settle steps of a reset; unlike
+    `data.time = 0` it stays inside the env mask of a masked launch).
 
     stale_first: the first substep is an `mj_step2` on the position/velocity
     stage left by `reset()` (qpos0), applied to the current state -- the order
@@ -562,11 +566,11 @@ class Physics(_control.Physics):
     if self._profiling:
       self._batch.timer_start()
     if isinstance(ctrl, tuple):
-      if stale_first:
-        raise ValueError('stale_first applies to settle steps (no new control)')
+      if stale_first or zero_time:
+        raise ValueError('stale_first / zero_time apply to settle steps (no new control)')
       self._batch.step_device(ctrl[1], ctrl[2], ctrl[3], n_sub_steps, outputs)
     else:
-      self._batch.step_host(ctrl, n_sub_steps, outputs, stale_first)
+      self._batch.step_host(ctrl, n_sub_steps, outputs, stale_first, zero_time)
     if self._profiling:
       ms, _ = self._batch.timer_stop()
       self._profile_seconds += ms*1e-3
@@ -607,6 +611,22 @@ class Physics(_control.Physics):
       logging.warning(message)
 
   check_divergence = check_invalid_state
+
+  # -- per-env episodes ---------------------------------------
+  def enable_episodes(self, step_limit=0):
+    """Every env gets a step counter and done bits on the device: an
+    output-producing `step` counts, raises `wrapper.DONE_LIMIT` at `step_limit`
+    (0: none) and `wrapper.DONE_BAD_STATE` for an env that raised a warning, and
+    leaves a done env frozen until `Task.reset_done` (or a reset) starts its next
+    episode.  Step with check=False: a bad state is a done flag, not an error."""
+    self._batch.episodes_enable(step_limit)
+
+  def episode_steps(self):
+    return self._batch.episode_read(wrapper.EPISODE_STEP)
+
+  def episode_done(self):
+    """int32 [B] of wrapper.DONE_* bits."""
+    return self._batch.episode_read(wrapper.EPISODE_DONE)
 
   def _ensure_aux(self):
     """xpos/xmat/qacc are written only once somebody asked for them; from then
@@ -702,6 +722,8 @@ class Physics(_control.Physics):
       ('ctrl', wrapper.FIELD_CTRL), ('taskdata', wrapper.FIELD_TASKDATA),
       ('episode_return', wrapper.FIELD_RETURN), ('warn', wrapper.FIELD_WARN))
 
+  _EPISODE_ARRAYS = (wrapper.EPISODE_STEP, wrapper.EPISODE_DONE, wrapper.EPISODE_MASK)
+
   @staticmethod
   def _checkpoint_path(path):
     path = str(path)
@@ -723,6 +745,9 @@ class Physics(_control.Physics):
     """
     b = self._batch
     arrays = {name: b.read(field) for name, field in self._CHECKPOINT_FIELDS}
+    if b.episodes:                # the episode block: step counts, done bits, env mask
+      arrays['episode_block'] = np.stack([b.episode_read(k) for k in self._EPISODE_ARRAYS])
+      arrays['episode_step_limit'] = np.array(b.step_limit)
     if self._params.per_env:      # the block as the device holds it + the fp64 values
       arrays['modelparam'] = b.read(wrapper.FIELD_MODELPARAM)
       arrays['per_env'] = np.array(','.join(self._params.per_env))
@@ -765,8 +790,18 @@ class Physics(_control.Physics):
         self._batch.write(wrapper.FIELD_MODELPARAM, z['modelparam'])
         self._params.load_block(
             z['modelparam'], {n: z['modelparam_' + n] for n in self._params.per_env})
+      if self._batch.episodes != ('episode_block' in z.files):
+        raise ValueError('checkpoint was written {} per-env episodes, this batch runs {} them'
+                         .format(*(('with', 'without') if 'episode_block' in z.files
+                                   else ('without', 'with'))))
       for name, field in self._CHECKPOINT_FIELDS:
         self._batch.write(field, z[name])
+      if self._batch.episodes:
+        if int(z['episode_step_limit']) != self._batch.step_limit:
+          raise ValueError('checkpoint was written with a step limit of {}, this batch has {}'
+                           .format(int(z['episode_step_limit']), self._batch.step_limit))
+        for k, which in enumerate(self._EPISODE_ARRAYS):
+          self._batch.episode_write(which, z['episode_block'][k])
       step_count = int(z['step_count'])
     self._warn_seen = self._batch.read(wrapper.FIELD_WARN).copy()
     self._pending_ctrl = None

@@ -64,8 +64,13 @@ class Cheetah(base.Task):
     # takes them right after overwriting qpos, without a forward pass, so its
     # first mj_step2 still works on the mass matrix, bias and contacts that
     # reset_context computed at qpos0: `stale_first`.
-    physics.step(_SETTLE_STEPS, outputs=False, stale_first=True)
-    physics.data.time = 0
+    if self._device_init:
+      # The episode starts at time 0: stored by the settle launch itself, so that
+      # under the env mask of `reset_done` the other envs keep their clocks.
+      physics.step(_SETTLE_STEPS, outputs=False, stale_first=True, zero_time=True)
+    else:
+      physics.step(_SETTLE_STEPS, outputs=False, stale_first=True)
+      physics.data.time = 0
     super().initialize_episode(physics)
 
   def get_observation(self, physics):

@@ -98,9 +98,10 @@ class Humanoid(base.Task):
     n = batch.nenv
     if self._device_init:
       batch.init_episode(self.device_seed())
+      selected = self.selected_envs(physics)    # (the envs of a `reset_done` pass)
       for _ in range(_MAX_REJECTION_ROUNDS):
         physics.after_reset()
-        if not np.any(np.atleast_1d(physics.data.ncon) > 0):
+        if not np.any(np.atleast_1d(physics.data.ncon)[selected] > 0):
           break
         batch.init_episode(self.device_seed(), only_colliding=True)
     else:

@@ -43,6 +43,19 @@ def field_tensor(batch, field):
   return t
 
 
+def episode_tensor(batch, which):
+  """int32 [nenv] torch tensor aliasing an array of the batch's episode block
+  (`wrapper.EPISODE_STEP`, `EPISODE_DONE`, `EPISODE_MASK`)."""
+  import torch
+  ptr = batch.episode_ptr(which)
+  if not ptr:
+    raise wrapper.Error('the batch has no episode block (episodes_enable)')
+  arr = _DeviceArray(ptr, (batch.nenv,), np.int32, batch)
+  t = torch.as_tensor(arr, device=torch.device('cuda', batch.model.device_id))
+  t._dmc_owner = arr               # pylint: disable=protected-access
+  return t
+
+
 def use_current_stream(batch):
   """Launch the batch's kernels on torch's current stream of its device."""
   import torch

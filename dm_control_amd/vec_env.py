@@ -14,7 +14,17 @@ Two I/O modes:
   * torch (`torch_io=True`): actions are CUDA tensors read in place, results
     are CUDA tensors aliasing the kernel's output buffers, everything runs on
     torch's current stream -- no host round trip in the loop.
+
+By default the B envs share one episode (they start and end together).  With
+`per_env_episodes=True` every env has its own, like the workers of
+`SubprocVecEnv`: the step kernel counts each env's steps and raises its done
+bits on the device, `dones` is per env, an env that is done -- at the time limit
+or because its state went bad -- is re-initialised alone (`Task.reset_done`) and
+reports the first observation of its new episode, and `episode_offsets`
+staggers the first episodes.  A bad state never raises in this mode.
 """
+
+import math
 
 import numpy as np
 
@@ -28,7 +38,12 @@ class VecEnv:
 
   def __init__(self, domain_name, task_name, num_envs, seed=None,
                device=0, precision='f32', torch_io=False, task_kwargs=None,
-               environment_kwargs=None, per_env=()):
+               environment_kwargs=None, per_env=(), per_env_episodes=False,
+               episode_offsets=None):
+    """per_env_episodes: every env ends and restarts its episodes on its own
+    (needs device_init, the default of torch mode).  episode_offsets: None,
+    'staggered' (env e starts e/B of the way into its first episode) or int [B]:
+    the step count every env's first episode starts with after `reset()`."""
     env_kw = dict(environment_kwargs or {})
     if per_env:        # model fields read per env (Physics.set_model_params)
       env_kw['per_env'] = tuple(per_env)
@@ -46,6 +61,28 @@ class VecEnv:
     self._nsub = self._env._n_sub_steps          # pylint: disable=protected-access
     self._step_limit = self._env._step_limit     # pylint: disable=protected-access
     self._count = 0
+    self._per_env = bool(per_env_episodes)
+    if self._per_env:
+      if not env_kw['device_init']:
+        raise ValueError('per_env_episodes=True needs device_init=True: the host-RNG '
+                         'recipes redraw the whole batch')
+      limit = 0 if math.isinf(self._step_limit) else max(1, int(math.ceil(self._step_limit)))
+      if episode_offsets is None:
+        offsets = np.zeros(self.num_envs, np.int32)
+      elif isinstance(episode_offsets, str):
+        if episode_offsets != 'staggered' or not limit:
+          raise ValueError("episode_offsets: None, 'staggered' (with a time limit) or int [B]")
+        offsets = (np.arange(self.num_envs, dtype=np.int64)*limit//self.num_envs).astype(np.int32)
+      else:
+        offsets = np.asarray(episode_offsets, np.int32)
+        if offsets.shape != (self.num_envs,):
+          raise ValueError('episode_offsets must have shape (%d,)' % self.num_envs)
+      self._offsets = offsets
+      self._physics.enable_episodes(limit)
+      # the humanoid's rejection loop depends on the data: it runs only when needed
+      self._pass_needs_done = domain_name == 'humanoid'
+    elif episode_offsets is not None:
+      raise ValueError('episode_offsets needs per_env_episodes=True')
     spec = self._env.action_spec()
     self.action_low, self.action_high = spec.minimum, spec.maximum
     self.action_dim = int(spec.shape[0])
@@ -55,6 +92,8 @@ class VecEnv:
       tio.use_current_stream(self._batch)
       self._obs_t = tio.field_tensor(self._batch, wrapper.FIELD_OBS)
       self._rew_t = tio.field_tensor(self._batch, wrapper.FIELD_REWARD)
+      if self._per_env:
+        self._done_t = tio.episode_tensor(self._batch, wrapper.EPISODE_DONE)
 
   @property
   def environment(self):
@@ -66,6 +105,11 @@ class VecEnv:
 
   def reset(self):
     """Starts new episodes everywhere; returns obs [B, D]."""
+    if self._per_env:
+      with self._physics.reset_context():
+        self._env.task.initialize_episode(self._physics)
+      self._batch.episode_write(wrapper.EPISODE_STEP, self._offsets)
+      return self._obs_t.clone() if self._torch else self._physics.fused_observation()
     if self._torch:
       return self._reset_torch()
     self._count = 0
@@ -73,6 +117,8 @@ class VecEnv:
 
   def step(self, actions):
     """-> (obs [B, D], rewards [B], dones [B], infos list of dicts)."""
+    if self._per_env:
+      return self._step_per_env_torch(actions) if self._torch else self._step_per_env(actions)
     if self._torch:
       return self._step_torch(actions)
     ts = self._env.step(actions)
@@ -86,16 +132,36 @@ class VecEnv:
       obs = self._obs(self._env.reset())          # vec_env.py:346-352
     return obs, rewards, dones, infos
 
-  # -- torch mode ---------------------------------------------------------------
-  def _reset_torch(self):
-    physics = self._physics
-    with physics.reset_context():
-      self._env.task.initialize_episode(physics)
-    self._count = 0
-    return self._obs_t.clone()
+  # -- per-env episodes -----------------------------------------------------------
+  def _step_per_env(self, actions):
+    physics, task = self._physics, self._env.task
+    task.before_step(actions, physics)
+    physics.step(self._nsub, check=False)
+    obs, rewards = physics.fused_observation(), physics.fused_reward()
+    done = physics.episode_done()
+    infos = [{'bad_state': bool(d & wrapper.DONE_BAD_STATE)} for d in done]
+    if done.any():
+      for i in np.nonzero(done)[0]:
+        infos[i]['terminal_observation'] = obs[i].copy()
+      task.reset_done(physics)
+      obs = physics.fused_observation()
+    return obs, rewards, done != 0, infos
 
-  def _step_torch(self, actions):
-    import torch
+  def _step_per_env_torch(self, actions):
+    physics = self._physics
+    self._launch_torch(actions)
+    rewards = self._rew_t.clone()
+    dones = self._done_t != 0
+    infos = {'terminal_observation': self._obs_t.clone(),
+             'bad_state': (self._done_t & wrapper.DONE_BAD_STATE) != 0}
+    # The reset pass is issued every step without asking the device who is done:
+    # its launches find an empty mask and exit.
+    if not self._pass_needs_done or bool(dones.any()):
+      self._env.task.reset_done(physics)
+    return self._obs_t.clone(), rewards, dones, infos
+
+  # -- torch mode ---------------------------------------------------------------
+  def _launch_torch(self, actions):
     if not actions.is_cuda:
       raise ValueError('torch_io=True expects CUDA action tensors')
     a = actions.to(self._obs_t.dtype)
@@ -105,9 +171,19 @@ class VecEnv:
     if a.stride(1) != 1:
       a = a.contiguous()
     self._keepalive = a
+    self._physics.set_control_device(a.data_ptr(), a.stride(1), a.stride(0))
+    self._physics.step(self._nsub, check=False)
+
+  def _reset_torch(self):
     physics = self._physics
-    physics.set_control_device(a.data_ptr(), a.stride(1), a.stride(0))
-    physics.step(self._nsub, check=False)
+    with physics.reset_context():
+      self._env.task.initialize_episode(physics)
+    self._count = 0
+    return self._obs_t.clone()
+
+  def _step_torch(self, actions):
+    import torch
+    self._launch_torch(actions)
     self._count += 1
     done = self._count >= self._step_limit
     rewards = self._rew_t.clone()

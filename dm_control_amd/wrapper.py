@@ -10,6 +10,7 @@ There is no CPU fallback: if the library cannot be loaded, or no MI355X-class
 device is present, construction raises `Error`.
 """
 
+import contextlib
 import ctypes
 import os
 import sys
@@ -45,6 +46,11 @@ globals().update(('FIELD_' + f[0], k) for k, f in enumerate(FIELDS))
 
 # bits of `want_outputs` (DMC_STEP_* of the header)
 STEP_OUTPUTS, STEP_STALE_FIRST = 1, 2
+STEP_ZERO_TIME = 4   # enum dmc_step_bit
+# enum dmc_episode_array: the int32 [nenv] arrays of the episode block
+EPISODE_STEP, EPISODE_DONE, EPISODE_MASK = 0, 1, 2
+# enum dmc_done_bit
+DONE_LIMIT, DONE_BAD_STATE = 1, 2
 
 
 class Error(Exception):
@@ -93,6 +99,12 @@ SIGNATURES = {
     'dmc_batch_device_ptr': (_vp, [_vp, _ci]),
     'dmc_batch_clear_warnings': (_ci, [_vp]),
     'dmc_batch_copy_state': (_ci, [_vp, _vp]),
+    'dmc_batch_episodes_enable': (_ci, [_vp, _ci]),
+    'dmc_batch_episode_ptr': (_vp, [_vp, _ci]),
+    'dmc_batch_episode_read': (_ci, [_vp, _ci, _vp, _cs]),
+    'dmc_batch_episode_write': (_ci, [_vp, _ci, _vp, _cs]),
+    'dmc_batch_mask_from_done': (_ci, [_vp]),
+    'dmc_batch_set_masked': (_ci, [_vp, _ci]),
     'dmc_batch_sync': (_ci, [_vp]),
     'dmc_batch_stream': (_vp, [_vp]),
     'dmc_batch_set_stream': (_ci, [_vp, _vp, _ci]),
@@ -212,6 +224,9 @@ class HipBatch:
     self.model = model  # keeps the module alive (core.py:643)
     self.nenv = int(nenv)
     self.ptr = _vp()
+    self.is_masked = False      # inside `masked()`
+    self.episodes = False       # after `episodes_enable`
+    self.step_limit = 0
     _check(self._lib.dmc_batch_create(model.ptr, self.nenv,
                                       ctypes.byref(self.ptr)))
 
@@ -283,13 +298,16 @@ class HipBatch:
   def forward(self, count_contacts=False):
     _check(self._lib.dmc_batch_forward(self.ptr, int(count_contacts)))
 
-  def step_host(self, ctrl, nsub=1, want_outputs=True, stale_first=False):
+  def step_host(self, ctrl, nsub=1, want_outputs=True, stale_first=False,
+                zero_time=False):
     """ctrl: host array [nenv, nu] (agent layout) or None.
 
     stale_first: DMC_STEP_STALE_FIRST (the first substep takes its acceleration
-    from the reset state; the reference cheetah's first settle step)."""
+    from the reset state; the reference cheetah's first settle step).
+    zero_time: DMC_STEP_ZERO_TIME (the stepped envs end with time 0)."""
     want_outputs = ((STEP_OUTPUTS if want_outputs else 0) |
-                    (STEP_STALE_FIRST if stale_first else 0))
+                    (STEP_STALE_FIRST if stale_first else 0) |
+                    (STEP_ZERO_TIME if zero_time else 0))
     if ctrl is None:
       _check(self._lib.dmc_batch_step(self.ptr, None, 0, 0, 0, nsub,
                                       want_outputs))
@@ -314,11 +332,56 @@ class HipBatch:
     _check(self._lib.dmc_batch_step_n(self.ptr, ctrl_ptr, stride_k, stride_env,
                                       stride_t, nsteps, nsub, int(want_outputs)))
 
+  # -- per-env episodes --------------------------------------------------------
+  def episodes_enable(self, step_limit=0):
+    """Allocates the episode block (step counts, done bits, env mask; zeroed).
+    From now on output-producing steps count and freeze per env, see
+    include/dmc_hip.h.  step_limit <= 0: no time limit."""
+    _check(self._lib.dmc_batch_episodes_enable(self.ptr, int(step_limit)))
+    self.episodes, self.step_limit = True, int(step_limit)
+
+  def episode_ptr(self, which):
+    return self._lib.dmc_batch_episode_ptr(self.ptr, which)
+
+  def episode_read(self, which):
+    out = np.empty(self.nenv, np.int32)
+    _check(self._lib.dmc_batch_episode_read(self.ptr, which, out.ctypes.data, out.nbytes))
+    return out
+
+  def episode_write(self, which, array):
+    a = np.ascontiguousarray(array, dtype=np.int32)
+    if a.shape != (self.nenv,):
+      raise ValueError('expected shape ({},), got {}'.format(self.nenv, a.shape))
+    _check(self._lib.dmc_batch_episode_write(self.ptr, which, a.ctypes.data, a.nbytes))
+
+  def mask_from_done(self):
+    """mask <- done, on the batch's stream (no host synchronisation)."""
+    _check(self._lib.dmc_batch_mask_from_done(self.ptr))
+
+  def set_masked(self, on):
+    _check(self._lib.dmc_batch_set_masked(self.ptr, int(bool(on))))
+    self.is_masked = bool(on)
+
+  @contextlib.contextmanager
+  def masked(self, mask=None):
+    """Inside, init_episode / forward / step leave envs with mask[e] == 0 alone.
+    mask: int or bool [nenv] to upload first (a host write, it synchronises);
+    None: the mask the device holds (`mask_from_done`, an earlier upload)."""
+    if mask is not None:
+      self.set_masked(True)      # (allocates the block on first use)
+      self.episode_write(EPISODE_MASK, np.asarray(mask) != 0)
+    self.set_masked(True)
+    try:
+      yield self
+    finally:
+      self.set_masked(False)
+
   def clear_warnings(self):
     _check(self._lib.dmc_batch_clear_warnings(self.ptr))
 
   def copy_state_from(self, other):
     _check(self._lib.dmc_batch_copy_state(self.ptr, other.ptr))
+    self.episodes, self.step_limit = other.episodes, other.step_limit
 
   def stream(self):
     return self._lib.dmc_batch_stream(self.ptr)

@@ -100,7 +100,9 @@ typedef struct dmc_model_info {
 /* 101: dmc_model_info gained `nmodelparam` at its end and DMC_FIELD_MODELPARAM exists; a
  * caller built against the 100 header must be rebuilt (dmc_model_get_info fills the whole
  * struct)
- * 102: dmc_model_info gained `seq_launch` at its end (same rule) */
+ * 102: dmc_model_info gained `seq_launch` at its end (same rule)
+ * 103: per-env episodes (dmc_batch_episodes_enable ... dmc_batch_set_masked, DMC_STEP_ZERO_TIME);
+ *      code objects export `dmc_episode_caps`; older ones still load and step */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
@@ -170,6 +172,10 @@ int dmc_batch_forward(dmc_batch* batch, int count_contacts);
                                   * rewrites qpos after reset_context's mj_forward and
                                   * steps without a forward pass
                                   * (suite/cheetah.py:63-77, engine.py:149-166) */
+/* a further bit of `want_outputs` (version 103 code objects): store time = 0 for the
+ * envs the launch stepped -- the settle steps of a reset that runs under an env mask,
+ * where a whole-field write of DMC_FIELD_TIME would touch the other envs */
+enum dmc_step_bit { DMC_STEP_ZERO_TIME = 4 };
 
 /* nsub x Physics.step, then observation + reward.
  * ctrl: element (k, env) at ctrl[k*stride_k + env*stride_env] (in reals);
@@ -213,6 +219,42 @@ int dmc_batch_set_stream(dmc_batch* batch, void* stream, int external);
 /* the batch's hipStream_t, for callers that enqueue their own work behind the
  * step (e.g. torch.cuda.ExternalStream) */
 void* dmc_batch_stream(dmc_batch* batch);
+
+/* Per-env episodes (version 103).  The episode block is three device int32[nenv]
+ * arrays next to the fields (not dmc_fields): the control steps of every env's
+ * episode, its done bits, and the env mask of masked launches.
+ *
+ * dmc_batch_episodes_enable allocates and zeroes the block; from then on
+ *   - an output-producing dmc_batch_step skips every env whose done word is nonzero
+ *     (it stays frozen, every field bit for bit, until it is re-initialised), adds 1
+ *     to the step count of every env it stepped and sets that env's done word to
+ *     DMC_DONE_LIMIT (step_limit > 0 and count >= step_limit) | DMC_DONE_BAD_STATE (the
+ *     launch raised a DMC_FIELD_WARN bit for the env: mj_checkPos put it back to qpos0);
+ *     settle steps (no outputs) neither count nor skip;
+ *   - dmc_batch_init_episode and dmc_batch_reset zero the step count, the done word and
+ *     the warning mask of every env they write;
+ *   - dmc_batch_step_n takes one launch per control step.
+ * dmc_batch_set_masked(on): while on, dmc_batch_init_episode, dmc_batch_forward and
+ * dmc_batch_step leave every env with mask[e] == 0 alone -- all of its fields and its
+ * part of the episode block are bit-identical after the launch; only_colliding
+ * composes (both conditions must hold).  dmc_batch_reset always covers the batch.
+ * dmc_batch_mask_from_done copies done -> mask on the batch's stream (no host
+ * synchronisation): the mask of a reset pass, which survives the init launch
+ * clearing the done words.  None of these calls, nor a masked launch, waits for the
+ * device; dmc_batch_episode_read / _write do (whole arrays, nenv*4 bytes).
+ * Code objects of team mode, and ones built before version 103, are refused with a
+ * message by every entry point that would need the flags. */
+enum dmc_episode_array {
+  DMC_EPISODE_STEP = 0, DMC_EPISODE_DONE = 1, DMC_EPISODE_MASK = 2, DMC_EPISODE_COUNT = 3
+};
+enum dmc_done_bit { DMC_DONE_LIMIT = 1, DMC_DONE_BAD_STATE = 2 };
+int dmc_batch_episodes_enable(dmc_batch* batch, int step_limit);
+/* borrowed device pointer (NULL before the block exists); lifetime = the batch handle */
+void* dmc_batch_episode_ptr(dmc_batch* batch, int which);
+int dmc_batch_episode_read(dmc_batch* batch, int which, int* dst, size_t bytes);
+int dmc_batch_episode_write(dmc_batch* batch, int which, const int* src, size_t bytes);
+int dmc_batch_mask_from_done(dmc_batch* batch);
+int dmc_batch_set_masked(dmc_batch* batch, int on);
 
 /* timing of the step kernel on the batch's own stream (HIP events around the
  * launches issued since dmc_batch_timer_start); returns accumulated device
