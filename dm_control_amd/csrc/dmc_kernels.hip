@@ -2271,10 +2271,13 @@ DEV int sphere_sphere(RawCon* c, real margin, const real* p1, const real* p2,
   const real dist = len - r1 - r2;
   if (dist > margin) return 0;
   c->dist = dist;
-#ifdef DMC_COOP_BUILD
-  // selects per component: as an if / else over a loop LLVM turned the stores
-  // into a dynamically indexed stack slot (scratch traffic from 2048 waves).
-  // Only in the several-lanes build, for the reason given at put_slot().
+#if defined(DMC_COOP_BUILD) || (!defined(DMC_REAL_IS_DOUBLE) && !DMC_GENERIC_BUILD)
+  // selects per component: as an if / else over a loop LLVM sank the stores
+  // through a pointer that is one stack slot or another (scratch traffic from
+  // 2048 waves; in the unrolled fp32 one-lane build 24 bytes per lane, where a
+  // lone wave waits out every round trip, in each of the unrolled pairs that
+  // reach this point).  Not in the other one-lane builds, for the reason given
+  // at put_slot().
   const bool apart = !(len < DMC_MINVAL);
   c->frame[0] = apart ? dif[0]/len : R(1);
   c->frame[1] = apart ? dif[1]/len : R(0);
