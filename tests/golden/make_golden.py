@@ -269,6 +269,51 @@ def tasks_golden():
         dist=dist, ctrl=ctrl.tolist(),
         reward=float(point_mass.PointMass(randomize_gains=False,
                                           random=0).get_reward(P()))))
+
+  # get_observation of the domains whose records above hold none: key order and
+  # the reading each key takes, on stub physics whose readings are canned
+  # vectors of the real widths (a stream of its own: the records above stay)
+  rs = np.random.RandomState(11)
+
+  def observe(task, base, readings):
+    class P(base):
+      pass
+    for name, value in readings.items():
+      if name != 'qpos':
+        setattr(P, name, (lambda v: lambda self: v)(value))
+    p = P()
+    if 'qpos' in readings:
+      p.data = types.SimpleNamespace(qpos=readings['qpos'])
+    obs = task.get_observation(p)
+    return dict(keys=list(obs.keys()),
+                values={k: np.ravel(v).tolist() for k, v in obs.items()},
+                readings={k: np.ravel(v).tolist() for k, v in readings.items()})
+  canned = lambda width: rs.uniform(-1, 1, width)
+  out['observations'] = {
+      'cheetah': observe(cheetah.Cheetah(random=0), cheetah.Physics,
+                         dict(qpos=canned(9), velocity=canned(9))),
+      'humanoid': observe(
+          humanoid.Humanoid(move_speed=1, pure_state=False, random=0), humanoid.Physics,
+          dict(joint_angles=canned(21), head_height=canned(1)[0], extremities=canned(12),
+               torso_vertical_orientation=canned(3), center_of_mass_velocity=canned(3),
+               velocity=canned(27))),
+      'humanoid_pure_state': observe(
+          humanoid.Humanoid(move_speed=10, pure_state=True, random=0), humanoid.Physics,
+          dict(position=canned(28), velocity=canned(27))),
+      'walker': observe(walker.PlanarWalker(move_speed=1, random=0), walker.Physics,
+                        dict(orientations=canned(14), torso_height=canned(1)[0],
+                             velocity=canned(9))),
+      'pendulum': observe(pendulum.SwingUp(random=0), pendulum.Physics,
+                          dict(pole_orientation=canned(2), angular_velocity=canned(1))),
+      'hopper': observe(hopper.Hopper(hopping=True, random=0), hopper.Physics,
+                        dict(qpos=canned(7), velocity=canned(7), touch=canned(2))),
+      'reacher': observe(reacher.Reacher(target_size=0.05, random=0), reacher.Physics,
+                         dict(position=canned(2), finger_to_target=canned(2),
+                              velocity=canned(2))),
+      'point_mass': observe(point_mass.PointMass(randomize_gains=False, random=0),
+                            point_mass.Physics,
+                            dict(position=canned(2), velocity=canned(2))),
+  }
   return out
 
 

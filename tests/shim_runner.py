@@ -202,3 +202,77 @@ def compare(rows, models, qpos, qvel, ctrl, steps, before_step=None):
     np.testing.assert_allclose(state[nq:], d.qvel, rtol=0, atol=1e-8)
   assert len(rows) == steps*len(models)
   return touched, datas
+
+
+OBSERVE_FIELDS = ('qpos', 'qvel', 'obs', 'reward', 'sensordata', 'xpos', 'xmat', 'warn')
+
+
+def run_observe(exe, qpos, qvel, ctrl, taskdata=None, nsub=1, task_param_i=0,
+                task_param_r=0.0, layout=0, timeout=900):
+  """The harness's observe mode over the envs qpos[e], qvel[e], ctrl[e],
+  taskdata[e]: dmc_observe, then one dmc_step of `nsub` substeps.  Returns
+  ({field: [nenv, k]} after dmc_observe, the same after dmc_step), every value
+  the word the kernel wrote (17 significant digits)."""
+  n = len(qpos)
+  text = '%d %d %d %.17g %d\n' % (n, nsub, task_param_i, task_param_r, layout)
+  for e in range(n):
+    values = np.concatenate([qpos[e], qvel[e], ctrl[e], [] if taskdata is None else taskdata[e]])
+    text += ' '.join('%.17g' % x for x in values) + '\n'
+  env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0')
+  out = subprocess.run([exe, 'observe'], input=text, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, universal_newlines=True, env=env, timeout=timeout)
+  assert out.returncode == 0, out.stderr[-3000:]
+  passes = []
+  for tag in ('OBSERVE', 'STEPPED'):
+    rows = [line.split('|') for line in out.stdout.splitlines() if line.startswith(tag + ' ')]
+    assert [int(r[0].split()[1]) for r in rows] == list(range(n)), tag
+    fields = {}
+    for i, name in enumerate(OBSERVE_FIELDS):
+      cols = [r[i].split()[2 if i == 0 else 0:] for r in rows]
+      fields[name] = np.array([[float(x) for x in c] for c in cols]).reshape(n, -1)
+    passes.append(fields)
+  return passes[0], passes[1], out.stdout
+
+
+def compare_observe(got, model, task, task_param_i, task_param_r, ctrl, taskdata, f64):
+  """One pass of `run_observe` against tests/output_model.py evaluated at the
+  state the pass printed, under the bounds of the device tests
+  (tests/test_gpu_outputs.py): fp64 1e-9 in `helpers.rel_err` form, fp32 the
+  model's per-class bound, copies of the state exact.  Touch entries: the
+  observation is log1p of the sensor."""
+  import output_model as M
+  real = np.float64 if f64 else np.float32
+  as_stored = lambda a: None if a is None else np.asarray(a, np.float64).astype(real).astype(
+      np.float64)
+  want = M.evaluate(model, task, task_param_i, (task_param_r,), got['qpos'], got['qvel'],
+                    as_stored(ctrl), as_stored(taskdata))
+  n = len(want.reward)
+  assert not got['warn'].any()
+  scale = M.scales(want)
+  tol = {k: 1e-9*scale[k] for k in M.CLASSES + ('state',)} if f64 else M.fp32_tolerances(want)
+  keep = ~M.excluded(want, tol)
+  assert keep.all(), 'a case state within rounding of a margin-0 bound'
+  checks = [('pos', 'xpos', got['xpos'], want.xpos.reshape(n, -1)),
+            ('rot', 'xmat', got['xmat'], want.xmat.reshape(n, -1)),
+            ('reward', 'reward', got['reward'], want.reward.reshape(n, 1))]
+  for name, g, w, kinds in (('obs', got['obs'], want.obs, want.obs_kinds),
+                            ('sensordata', got['sensordata'], want.sensordata,
+                             want.sensor_kinds)):
+    kinds = np.array(kinds)
+    for kind in M.CLASSES + ('state',):
+      if (kinds == kind).any():
+        checks.append((kind, '%s.%s' % (name, kind), g[:, kinds == kind], w[:, kinds == kind]))
+  for kind, name, g, w in checks:
+    assert g.shape == w.shape, name
+    if kind == 'state':
+      np.testing.assert_array_equal(g, w, err_msg=name)
+    elif f64:
+      assert helpers.rel_err(g, w).max() <= 1e-9, (name, helpers.rel_err(g, w).max())
+    else:
+      err = np.abs(g - w).max(axis=1)/(M.EPS32*scale[kind])
+      assert err.max() <= M.bound_in_eps(kind), (name, int(err.argmax()), err.max())
+  touch_obs = np.array(want.obs_kinds) == 'touch'
+  if touch_obs.any():
+    touch = got['sensordata'][:, np.array(want.sensor_kinds) == 'touch']
+    eps = np.finfo(real).eps
+    np.testing.assert_allclose(got['obs'][:, touch_obs], np.log1p(touch), rtol=8*eps, atol=8*eps)

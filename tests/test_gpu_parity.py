@@ -379,12 +379,134 @@ def test_full_size_properties_cheetah_8192():
   np.testing.assert_allclose(rew, expect, atol=1e-6)
 
 
+# (task_param_i, task_param_r) the suite hands the device per task
+_TASK_PARAMS = {
+    ('cartpole', 'swingup'): (2, ()), ('cartpole', 'balance_sparse'): (1, ()),
+    ('cheetah', 'run'): (0, ()), ('humanoid', 'walk'): (0, (1.0,)),
+    ('humanoid', 'stand'): (0, (0.0,)), ('humanoid', 'run_pure_state'): (0, (10.0,)),
+    ('walker', 'run'): (0, (8.0,)), ('walker', 'stand'): (0, (0.0,)),
+    ('pendulum', 'swingup'): (0, ()), ('acrobot', 'swingup'): (0, ()),
+    ('acrobot', 'swingup_sparse'): (1, ()), ('hopper', 'stand'): (0, ()),
+    ('hopper', 'hop'): (1, ()), ('reacher', 'easy'): (0, (0.05 + 0.01,)),
+    ('reacher', 'hard'): (0, (0.015 + 0.01,)), ('point_mass', 'easy'): (0, ())}
+
+
+def _check_time_step_against_output_model(physics, ts, domain, task):
+  """The TimeStep's observation (per key) and reward, and the host accessors the
+  tasks read, against tests/output_model.py evaluated at physics.data.qpos /
+  qvel / ctrl: expected values that share nothing with the device's frames
+  (bounds: output_model.py; the environments here are f32)."""
+  import output_model
+  model = physics.model
+  f64 = lambda a: np.asarray(a, np.float64)
+  qpos, qvel, ctrl = f64(physics.data.qpos), f64(physics.data.qvel), f64(physics.data.ctrl)
+  n = len(qpos)
+  taskdata = (f64(physics.batch.read(W.FIELD_TASKDATA)).T
+              if physics.batch.model.info.ntaskdata > 0 else None)
+  param_i, param_r = _TASK_PARAMS[domain, task]
+  want = output_model.evaluate(model, helpers.TASKS[domain], param_i, param_r, qpos, qvel,
+                               ctrl, taskdata)
+  assert physics.batch.model.dtype == np.float32
+  tol = output_model.fp32_tolerances(want)
+
+  def check(name, got, expected, kind):
+    got, expected = f64(got).reshape(n, -1), f64(expected).reshape(n, -1)
+    assert got.shape == expected.shape, name
+    err = np.abs(got - expected).max(axis=1)
+    assert np.all(err <= tol[kind]), (domain, task, name, int(np.argmax(err/np.maximum(
+        tol[kind], 1e-300))), err.max())
+  # A sample whose margin-0 input lies within that input's tolerance of a bound may
+  # take the other branch on the device.  Every margin-0 term of these tasks is a
+  # factor of the reward, so such a sample is either the model's value, or 0 (the
+  # device left the bounds), or, where the model itself is out of bounds, any
+  # value in [0, 1].  These states are not designed: cartpole balance starts with
+  # pole angles uniform in +-0.034 rad, and cos(angle) is within the rotation
+  # tolerance (14 eps32) of the cone's upper bound 1 for |angle| < 1.8e-3, about
+  # 5 % of the envs; a quarter of a batch of 64 is more than six sigma above that.
+  near = output_model.excluded(want, tol)
+  assert near.sum() <= 0.25*n, (domain, task, near.sum())
+  reward = f64(ts.reward)
+  err = np.abs(reward - want.reward)
+  assert np.all(err[~near] <= tol['reward'][~near]), (domain, task, err[~near].max())
+  other_branch = (np.abs(reward) <= tol['reward']) | (
+      (want.reward == 0) & (reward >= 0) & (reward <= 1))
+  assert np.all((err <= tol['reward']) | other_branch | ~near), (domain, task)
+  kinds = np.array(want.obs_kinds)
+  sens = f64(physics.data.sensordata).reshape(n, -1)
+  if task == 'run_pure_state':
+    np.testing.assert_array_equal(f64(ts.observation['position']), qpos)
+    np.testing.assert_array_equal(f64(ts.observation['velocity']), qvel)
+  else:
+    slices = output_model.obs_slices(domain)
+    assert list(ts.observation) == list(slices)
+    for key, sl in slices.items():
+      got = f64(ts.observation[key]).reshape(n, -1)
+      for kind in set(kinds[sl]):
+        cols = kinds[sl] == kind
+        if kind == 'touch':
+          touch = sens[:, np.array(want.sensor_kinds) == 'touch']
+          np.testing.assert_allclose(got[:, cols], np.log1p(touch), rtol=1e-6, atol=1e-6)
+        else:
+          check('observation[%r] (%s)' % (key, kind), got[:, cols], want.obs[:, sl][:, cols], kind)
+  modelled = np.array(want.sensor_kinds) != 'touch'
+  for kind in set(np.array(want.sensor_kinds)[modelled]) if modelled.any() else ():
+    cols = np.array(want.sensor_kinds) == kind
+    check('sensordata (%s)' % kind, sens[:, cols], want.sensordata[:, cols], kind)
+  term = {t.name: t.x for t in want.terms}
+  bodies = codegen.task_bodies(model, helpers.TASKS[domain])
+  zz = lambda b: want.xmat[:, b, 8]
+  if domain == 'cheetah':
+    check('speed', physics.speed(), want.subtree_linvel[:, bodies[0], 0], 'vel')
+  elif domain == 'humanoid':
+    torso, head = bodies[:2]
+    check('head_height', physics.head_height(), want.xpos[:, head, 2], 'pos')
+    check('torso_upright', physics.torso_upright(), zz(torso), 'rot')
+    check('center_of_mass_velocity', physics.center_of_mass_velocity(),
+          want.subtree_linvel[:, torso], 'vel')
+    check('torso_vertical_orientation', physics.torso_vertical_orientation(),
+          want.xmat[:, torso, 6:], 'rot')
+    np.testing.assert_array_equal(f64(physics.joint_angles()), qpos[:, 7:])
+    check('extremities', physics.extremities(),
+          want.obs[:, output_model.obs_slices('humanoid')['extremities']], 'pos')
+  elif domain == 'walker':
+    check('torso_upright', physics.torso_upright(), zz(bodies[0]), 'rot')
+    check('torso_height', physics.torso_height(), want.xpos[:, bodies[0], 2], 'pos')
+    check('horizontal_velocity', physics.horizontal_velocity(),
+          want.subtree_linvel[:, bodies[0], 0], 'vel')
+    check('orientations', physics.orientations(),
+          want.obs[:, output_model.obs_slices('walker')['orientations']], 'rot')
+  elif domain == 'hopper':
+    check('height', physics.height(), term['height'], 'pos')
+    check('speed', physics.speed(), want.subtree_linvel[:, bodies[0], 0], 'vel')
+  elif domain == 'cartpole':
+    np.testing.assert_array_equal(f64(physics.cart_position()).reshape(n), qpos[:, 0])
+    np.testing.assert_array_equal(f64(physics.angular_vel()).reshape(n, -1), qvel[:, 1:])
+    check('pole_angle_cosine', physics.pole_angle_cosine(), zz(2), 'rot')
+    check('bounded_position', f64(physics.bounded_position())[:, 1:], want.obs[:, 1:3], 'rot')
+  elif domain == 'acrobot':
+    check('horizontal', physics.horizontal(), want.obs[:, 0:2], 'rot')
+    check('vertical', physics.vertical(), want.obs[:, 2:4], 'rot')
+    check('to_target', physics.to_target(), term['to_target'], 'pos')
+  elif domain == 'pendulum':
+    check('pole_vertical', physics.pole_vertical(), zz(bodies[0]), 'rot')
+    np.testing.assert_array_equal(f64(physics.angular_velocity()).reshape(n), qvel[:, 0])
+  elif domain == 'reacher':
+    check('finger_to_target', physics.finger_to_target(),
+          want.obs[:, output_model.obs_slices('reacher')['to_target']], 'pos')
+    check('finger_to_target_dist', physics.finger_to_target_dist(), term['finger_to_target'],
+          'pos')
+  elif domain == 'point_mass':
+    check('mass_to_target_dist', physics.mass_to_target_dist(), term['near'], 'pos')
+
+
 def test_fused_task_outputs_match_reference_formulas():
   """Device reward/observation vs the golden-validated host formulas."""
   for domain, task, nenv in (('cartpole', 'swingup', 64),
                              ('cartpole', 'balance_sparse', 64),
+                             ('cheetah', 'run', 32),
                              ('humanoid', 'walk', 32),
                              ('humanoid', 'stand', 32),
+                             ('humanoid', 'run_pure_state', 32),
                              ('walker', 'run', 32), ('walker', 'stand', 32),
                              ('pendulum', 'swingup', 64),
                              ('acrobot', 'swingup', 64),
@@ -417,6 +539,9 @@ def test_fused_task_outputs_match_reference_formulas():
         np.testing.assert_allclose(ts.observation['position'][i],
                                    [qpos[i, 0], xmat[i, 2, 8], xmat[i, 2, 2]],
                                    atol=1e-6)
+      elif domain == 'cheetah':
+        want = task_formulas.cheetah_reward(np.asarray(physics.data.sensordata)[i, 0])
+        np.testing.assert_array_equal(ts.observation['position'][i], qpos[i, 1:])
       elif domain == 'walker':
         m = physics.model
         torso = m.name2id('torso', 'body')
@@ -472,7 +597,11 @@ def test_fused_task_outputs_match_reference_formulas():
         want = task_formulas.humanoid_reward(
             xpos[i, m.name2id('head', 'body'), 2],
             xmat[i, m.name2id('torso', 'body'), 8], ctrl[i], com,
-            1 if task == 'walk' else 0)
+            {'walk': 1, 'stand': 0, 'run_pure_state': 10}[task])
+        np.testing.assert_allclose(ts.reward[i], want, rtol=2e-4, atol=1e-7)
+        if task == 'run_pure_state':
+          assert list(ts.observation) == ['position', 'velocity']
+          continue
         torso = m.name2id('torso', 'body')
         r = xmat[i, torso].reshape(3, 3)
         ext = []
@@ -487,6 +616,7 @@ def test_fused_task_outputs_match_reference_formulas():
         np.testing.assert_allclose(ts.observation['torso_vertical'][i],
                                    r[2], atol=1e-6)
       np.testing.assert_allclose(ts.reward[i], want, rtol=2e-4, atol=1e-7)
+    _check_time_step_against_output_model(physics, ts, domain, task)
     physics.free()
 
 

@@ -291,3 +291,58 @@ def test_init_kernel_batch_creation_writes_the_compiled_defaults(domain, group, 
     shim_runner.compare_init(got, want, 8 if f64 else 4)
     if domain == 'point_mass':
       assert np.abs(got['taskdata']).max() > 0
+
+
+# ---------------------------------------------------------------------------
+# the output stage (the harness's observe mode): dmc_observe and one dmc_step
+# of the kernel sources against tests/output_model.py
+# ---------------------------------------------------------------------------
+# (shape: unroll for one env per lane, lanes per env for csrc/dmc_coop.hip)
+OBSERVE_SHAPES = {'one-lane-unrolled': dict(unroll=True), 'one-lane-rolled': dict(unroll=False),
+                  'g32': dict(group=32), 'g128': dict(group=128)}
+OBSERVE_DOMAINS = ('cheetah', 'hopper', 'walker', 'humanoid', 'cartpole')
+OBSERVE_NENV = 10          # designed states (every branch) and plausible ones; even: whole
+                           # workgroups of the two-envs-per-workgroup shape
+
+
+def _observe_envs(domain):
+  """Case states of tests/output_cases.py: spread over the designed block, so
+  that the few envs see most branches, plus two of the plausible block."""
+  import output_cases
+  model, qpos, qvel, ctrl, taskdata = output_cases.states(domain)
+  first = output_cases.NFIRST
+  pick = np.r_[np.linspace(first, output_cases.NENV - 1, OBSERVE_NENV - 2).astype(int), [1, 2]]
+  return (model, qpos[pick], qvel[pick], ctrl[pick],
+          None if taskdata is None else taskdata[pick])
+
+
+@pytest.mark.timeout(1500)
+@pytest.mark.parametrize('domain,shape,f64', [
+    pytest.param(d, s, f, id='%s-%s-%s' % (d, s, 'f64' if f else 'f32'))
+    for d in OBSERVE_DOMAINS for s in sorted(OBSERVE_SHAPES) for f in (True, False)
+    # (the humanoid ships with the several-lanes kernel only)
+    if not (d == 'humanoid' and s.startswith('one-lane'))])
+def test_output_stage_of_the_kernel_sources_matches_the_host_model(domain, shape, f64, tmp_path):
+  """Both kernels' own com_vel / subtree_vel / observe_stage / task layer /
+  output store, in dmc_observe and after a dmc_step, under ASan + UBSan with
+  buffers of exactly nenv envs; every variant of the domain's tasks.  One env
+  per lane: the observation through the LDS transpose (a partial workgroup)
+  and through the explicit strides must be the same words."""
+  import output_cases
+  model, qpos, qvel, ctrl, taskdata = _observe_envs(domain)
+  task = helpers.TASKS[domain]
+  exe = shim_runner.build(model, task, tmp_path, f64=f64, **OBSERVE_SHAPES[shape])
+  nsub = 2
+  for label, poles, param_i, param_r in output_cases.VARIANTS[domain]:
+    if poles is not None:
+      continue
+    r0 = param_r[0] if param_r else 0.0
+    observed, stepped, text = shim_runner.run_observe(
+        exe, qpos, qvel, ctrl, taskdata, nsub, param_i, r0, layout=0)
+    np.testing.assert_array_equal(observed['qpos'], qpos.astype(np.float64 if f64 else np.float32))
+    assert not np.array_equal(stepped['qpos'], observed['qpos'])
+    for got in (observed, stepped):
+      shim_runner.compare_observe(got, model, task, param_i, r0, ctrl, taskdata, f64)
+    if shape.startswith('one-lane'):
+      assert shim_runner.run_observe(exe, qpos, qvel, ctrl, taskdata, nsub, param_i, r0,
+                                     layout=1)[2] == text
