@@ -246,8 +246,10 @@ def task_sites(m, task):
   return out
 
 
-def capacities(m, pairs, ncon_max=None):
-  """Contact / constraint-row capacities of the per-env workspace."""
+def capacities(m, pairs, ncon_max=None, nefc_max=None):
+  """Contact / constraint-row capacities of the per-env workspace.  `nefc_max`
+  (tests of the row capacity only): the row capacity itself, in place of the
+  one that holds the rows of `ncon_max` contacts and of every limit."""
   per_pair = {mdl.GEOM_CAPSULE: 2, mdl.GEOM_BOX: 4}
   worst = 0
   worst_rows = 0
@@ -270,7 +272,8 @@ def capacities(m, pairs, ncon_max=None):
     ncon_max = min(worst, 32)
   rows_per_con = max([1] + [1 if mx['dim'] == 1 else 2*(mx['dim'] - 1)
                             for mx in mixed])
-  nefc_max = nlimit + min(worst_rows, ncon_max*rows_per_con)
+  if nefc_max is None:
+    nefc_max = nlimit + min(worst_rows, ncon_max*rows_per_con)
   return max(ncon_max, 1), max(nefc_max, 1)
 
 
@@ -402,7 +405,7 @@ def model_param_values(m, layout):
   return out
 
 
-def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=()):
+def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=(), nefc_max=None):
   """Returns the text of the constants header for model `m`.  `per_env`: fields
   the kernels read per env from the model-parameter block (model_param_layout);
   empty: every field is a compile-time table."""
@@ -413,7 +416,7 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=()):
     raise UnsupportedModelError('only the Newton solver is implemented')
   pairs = collision_pairs(m)
   mixed = [mix_pair(m, g1, g2) for g1, g2 in pairs]
-  ncon_max, nefc_max = capacities(m, pairs, ncon_max)
+  ncon_max, nefc_max = capacities(m, pairs, ncon_max, nefc_max)
   refsafe = not (m.opt.disableflags & mdl.DSBL_REFSAFE)
   dt = float(m.opt.timestep)
   if unroll is None:
@@ -792,10 +795,10 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=()):
   return '\n'.join(out) + '\n'
 
 
-def model_info(m, task=TASK_NONE, ncon_max=None):
+def model_info(m, task=TASK_NONE, ncon_max=None, nefc_max=None):
   """Sizes the host needs without loading the code object."""
   pairs = collision_pairs(m)
-  ncon_max, nefc_max = capacities(m, pairs, ncon_max)
+  ncon_max, nefc_max = capacities(m, pairs, ncon_max, nefc_max)
   return dict(nq=m.nq, nv=m.nv, nu=m.nu, nbody=m.nbody,
               nobs=observation_size(m, task), nsensordata=m.nsensordata,
               ncon_max=ncon_max, nefc_max=nefc_max, npair=len(pairs),

@@ -54,14 +54,17 @@ def case(name, nenv=None):
 
 
 def build(model, task, tmp_path, unroll=True, group=None, team=None, ncon_max=None,
-          per_env=(), sanitizer='address,undefined', f64=True, extra=(), name='harness'):
+          per_env=(), sanitizer='address,undefined', f64=True, extra=(), name='harness',
+          nefc_max=None):
   """Compiles tests/host_shim/harness.cpp around the kernel source of the shape:
   one env per lane (csrc/dmc_kernels.hip; `unroll`), `group` lanes per env
   (csrc/dmc_coop.hip; 128: 64 lanes and the helper wavefront), or team mode
   (`team` lanes share the env; `ncon_max`).  sanitizer None: the plain -O2 build
-  without contraction.  Returns the path of the program."""
-  header = tmp_path/'model.h'
-  text = codegen.generate_header(model, task, ncon_max=ncon_max, unroll=unroll, per_env=per_env)
+  without contraction.  `nefc_max`: a row capacity below what the contacts of
+  `ncon_max` need (no product build has one).  Returns the path of the program."""
+  header = tmp_path/(name + '.h')
+  text = codegen.generate_header(model, task, ncon_max=ncon_max, unroll=unroll, per_env=per_env,
+                                 nefc_max=nefc_max)
   header.write_text(text.replace('static __device__ constexpr', 'static constexpr'))
   if group:
     shape = ['-DDMC_GROUP=%d' % min(group, 64), '-DDMC_COOP_DUO=%d' % (group == 128)]
@@ -171,8 +174,13 @@ def compare_init(got, want, real_size, fields=INIT_FIELDS):
   return figure
 
 
-def oracle_at(model, qpos, qvel, ctrl):
-  d = oracle.OracleData(oracle.OracleModel(model))
+def oracle_at(model, qpos, qvel, ctrl, ncon_max=None, nefc_max=None):
+  om = oracle.OracleModel(model)
+  if ncon_max is not None:
+    om.set_int('nconmax', ncon_max)
+  if nefc_max is not None:
+    om.set_int('nefcmax', nefc_max)
+  d = oracle.OracleData(om)
   d.qpos[:] = qpos
   d.qvel[:] = qvel
   d.ctrl[:] = ctrl
@@ -180,13 +188,23 @@ def oracle_at(model, qpos, qvel, ctrl):
   return d
 
 
-def compare(rows, models, qpos, qvel, ctrl, steps, before_step=None):
+WARN_CONTACTFULL, WARN_CNSTRFULL = 2, 4     # csrc/dmc_args.h
+
+
+def compare(rows, models, qpos, qvel, ctrl, steps, before_step=None, expect=None):
   """Steps the oracle of env e on models[e] next to `rows` and asserts the
   counters and the state of every row; before_step(d) sees the oracle of a row
-  before it is stepped.  Returns (whether any step had constraint rows, the
-  oracles after the last step)."""
-  datas = [oracle_at(m, qpos[e], qvel[e], ctrl) for e, m in enumerate(models)]
+  before it is stepped.  expect None: no warning bit may be set.  expect =
+  dict(ncon_max=, nefc_max=): the oracle runs with these capacities, and the
+  warning word must be exactly the CONTACTFULL / CNSTRFULL bits of the steps so
+  far (the kernel's word is sticky) as the oracle's warning[1] / warning[2]
+  counters moved in the pass that made each step's contacts and rows -- and no
+  other counter of the oracle may move.  Returns (whether any step had
+  constraint rows, the oracles after the last step)."""
+  datas = [oracle_at(m, qpos[e], qvel[e], ctrl, **(expect or {})) for e, m in enumerate(models)]
   touched = False
+  counted = [np.zeros(8, int) for _ in models]
+  bits = [0]*len(models)
   for e, state, (ncon, nefc, iters, warn) in rows:
     d = datas[e]
     touched |= d.nefc > 0
@@ -195,8 +213,15 @@ def compare(rows, models, qpos, qvel, ctrl, steps, before_step=None):
     assert (ncon, nefc) == (d.ncon, d.nefc)
     if before_step:
       before_step(d)
+    if expect is not None:
+      moved = d.warning - counted[e]
+      counted[e] = d.warning.copy()
+      bits[e] |= (WARN_CONTACTFULL if moved[1] else 0) | (WARN_CNSTRFULL if moved[2] else 0)
+      assert not d.warning[[0, 3, 4, 5, 6, 7]].any(), d.warning
     d.physics_step()
-    assert warn == 0
+    assert warn == (0 if expect is None else bits[e]), (e, warn, bits[e])
+    if expect is not None:      # (the step itself: BADQACC, BADQPOS / BADQVEL of its step1)
+      assert not d.warning[[0, 3, 4, 5, 6, 7]].any(), d.warning
     nq = len(d.qpos)
     np.testing.assert_allclose(state[:nq], d.qpos, rtol=0, atol=1e-9)
     np.testing.assert_allclose(state[nq:], d.qvel, rtol=0, atol=1e-8)
