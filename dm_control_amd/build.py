@@ -230,10 +230,14 @@ Spec = collections.namedtuple(
 
 
 def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
-         per_env=()):
+         per_env=(), rollout=False):
   """Checks the arguments of `build_model` and resolves them into a `Spec`.
   Pure: reads the environment, touches no file and starts no process.
-  `per_env`: model fields the kernels read per env (codegen.PER_ENV_FIELDS)."""
+  `per_env`: model fields the kernels read per env (codegen.PER_ENV_FIELDS).
+  `rollout`: the rollout variant of the one-env-per-lane kernel (-DDMC_ROLLOUT=1)."""
+  if rollout and mode in ('coop', 'team'):
+    raise ValueError('rollout=True is built for the one-env-per-lane kernel '
+                     '(mode auto, unrolled or rolled), not for mode=%r' % mode)
   per_env = codegen.normalise_per_env(per_env)     # ValueError: unknown names
   if per_env and mode == 'team':
     raise codegen.UnsupportedModelError(
@@ -278,6 +282,9 @@ def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
     if mode in ('auto', 'unrolled'):
       tiers = (_UNROLLED,) + tiers if mode == 'auto' else (_UNROLLED,)
     source = 'dmc_kernels.hip'
+  if rollout:
+    # per-step outputs and the device MLP policy (csrc/dmc_kernels.hip, DMC_ROLLOUT)
+    flags += ('-DDMC_ROLLOUT=1',)
   return Spec(model, task, ncon_max, precision, mode, group, lds_budget, source,
               'f64' if precision == 'f64' else 'f32', flags, tiers, per_env)
 
@@ -461,7 +468,7 @@ def realise(spec_, force=False, keep_temps=False):
 
 def build_model(model, task=codegen.TASK_NONE, precision='f32',
                 ncon_max=None, force=False, keep_temps=False, extra_flags=None,
-                mode='auto', lds_budget=None, group=64, per_env=()):
+                mode='auto', lds_budget=None, group=64, per_env=(), rollout=False):
   """Generates the constants header for `model` and compiles its kernels.
 
   mode: "unrolled" (static indexing, per-lane state in registers), "rolled"
@@ -479,6 +486,10 @@ def build_model(model, task=codegen.TASK_NONE, precision='f32',
   varied build walks the same tiers: where its extra loads push it past the
   spill budget of a tier the default build fits, its `.verdict` says "over" and
   the next tier is taken.
+
+  rollout: True builds the rollout variant of the one-env-per-lane kernel
+  (`dmc_batch_rollout`: per-step outputs, device MLP policy); it walks the same
+  tiers and is refused (ValueError) for "coop" and "team".
   """
   return realise(spec(model, task, precision, ncon_max, extra_flags, mode,
-                      lds_budget, group, per_env), force, keep_temps)
+                      lds_budget, group, per_env, rollout), force, keep_temps)

@@ -58,6 +58,7 @@ struct dmc_model {
   hipFunction_t k_step = nullptr, k_observe = nullptr, k_init = nullptr;
   dmc_model_info info{};
   int episode_caps = 0;   // DMC_FLAG_* bits of the code object's dmc_episode_caps (0: it has none)
+  int rollout_caps = 0;   // the code object's dmc_rollout_caps (0: not a rollout build)
 };
 
 struct dmc_batch {
@@ -226,7 +227,8 @@ extern "C" {
 
 // 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM; 102: dmc_model_info.seq_launch;
 // 103: per-env episodes (dmc_batch_episodes_enable and what follows it in the header)
-int dmc_version(void) { return 103; }
+// 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout)
+int dmc_version(void) { return 104; }
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -438,6 +440,13 @@ int load_model(const char* path, const void* image, int device_id, dmc_model** o
     m->episode_caps = caps;
   else
     (void)hipGetLastError();   // an older code object: the episode entry points refuse it
+  DmcRolloutCaps rcaps = 0;
+  if (hipModuleGetGlobal(&dptr, &bytes, m->module, "dmc_rollout_caps") == hipSuccess &&
+      bytes >= sizeof rcaps &&
+      hipMemcpy(&rcaps, dptr, sizeof rcaps, hipMemcpyDeviceToHost) == hipSuccess)
+    m->rollout_caps = rcaps;
+  else
+    (void)hipGetLastError();   // not a rollout build: dmc_batch_rollout refuses it
   *out = m;
   return 0;
 }
@@ -707,6 +716,74 @@ int dmc_batch_step_n(dmc_batch* b, const void* ctrl, long long stride_k,
                     stride_t, chunk, 1, nsub,
                     t == 0 ? want_outputs : want_outputs & ~DMC_STEP_STALE_FIRST))
       return -1;
+    t += chunk;
+  }
+  return 0;
+}
+
+int dmc_model_rollout_caps(const dmc_model* model) { return model ? model->rollout_caps : 0; }
+
+int dmc_batch_rollout(dmc_batch* b, const dmc_rollout* r) {
+  if (!b || !r) return fail("dmc_batch_rollout: null argument");
+  const dmc_model_info& i = b->model->info;
+  const int caps = b->model->rollout_caps;
+  if (!(caps & DMC_ROLLOUT_CAP_OUTPUTS))
+    return fail("dmc_batch_rollout: this code object takes no rollouts; build the model "
+                "with rollout=True (the one-env-per-lane kernel, -DDMC_ROLLOUT=1)");
+  if (b->episodes || b->masked)
+    return fail("dmc_batch_rollout: rollouts are lock-step; the batch has %s",
+                b->episodes ? "per-env episodes enabled" : "an env mask set");
+  if (r->nsteps < 0) return fail("dmc_batch_rollout: nsteps must be >= 0");
+  if (r->nsub < 0) return fail("dmc_batch_rollout: nsub must be >= 0");
+  if (r->policy) {
+    const int cap = caps >> DMC_ROLLOUT_CAP_WIDTH_SHIFT;
+    if (!(caps & DMC_ROLLOUT_CAP_POLICY))
+      return fail("dmc_batch_rollout: this code object takes no policy");
+    if (r->nlayers != 1 && r->nlayers != 2)
+      return fail("dmc_batch_rollout: a policy has 1 or 2 hidden layers, not %d", r->nlayers);
+    for (int l = 0; l < r->nlayers; l++)
+      if (r->width[l] < 1 || r->width[l] > cap)
+        return fail("dmc_batch_rollout: hidden layer %d has %d units; this code object "
+                    "takes 1 to %d", l, r->width[l], cap);
+    if (r->width[r->nlayers] != i.nu)
+      return fail("dmc_batch_rollout: the policy puts out %d values, the model has %d controls",
+                  r->width[r->nlayers], i.nu);
+  }
+  HIP_TRY(hipSetDevice(b->model->device));
+  const long long rs = (long long)i.real_size;
+  const auto at = [rs](const void* p, long long words) -> void* {
+    return p ? (char*)p + words*rs : nullptr;
+  };
+  // one launch per chunk of control steps, every pointer advanced by the chunk
+  for (int t = 0; t < r->nsteps;) {
+    const int chunk = r->nsteps - t < DMC_SEQ_LAUNCH_MAX_STEPS ? r->nsteps - t
+                                                               : DMC_SEQ_LAUNCH_MAX_STEPS;
+    DmcArgs a;
+    fill_args(b, a);
+    a.nsub = r->nsub;
+    a.nsteps = chunk;
+    if (r->ctrl && i.nu > 0) {
+      a.flags |= DMC_FLAG_CTRL;
+      a.ctrl = at(r->ctrl, t*r->ctrl_stride_t);
+      a.ctrl_sk = r->ctrl_stride_k;
+      a.ctrl_se = r->ctrl_stride_env;
+      a.ctrl_st = r->ctrl_stride_t;
+    }
+    if (r->policy && i.nu > 0) {
+      a.flags |= DMC_FLAG_POLICY;
+      a.policy = r->policy;
+      a.policy_nlayers = r->nlayers;
+      a.policy_width[0] = r->width[0];
+      a.policy_width[1] = r->nlayers == 2 ? r->width[1] : 0;
+    }
+    a.reward_out = at(r->reward_out, t*r->reward_stride_t);
+    a.reward_out_st = r->reward_stride_t;
+    a.obs_out = at(r->obs_out, t*r->obs_stride_t);
+    a.obs_out_st = r->obs_stride_t;
+    a.action_out = i.nu > 0 ? at(r->action_out, t*r->action_stride_t) : nullptr;
+    a.action_out_st = r->action_stride_t;
+    if (launch(b, b->model->k_step, a, MODEL_SHAPED)) return -1;
+    if (b->timing) b->launches += chunk;   // (the timer's average stays per control step)
     t += chunk;
   }
   return 0;

@@ -43,6 +43,21 @@ struct DmcArgs {
   int* ep_step;            // [nenv] DMC_FLAG_EPISODES: control steps of the episode
   int* ep_done;            // [nenv] DMC_FLAG_EPISODES: DMC_EP_DONE_* bits, nonzero = frozen until re-initialised
   int step_limit;          // ep_done gets DMC_EP_DONE_LIMIT once ep_step >= step_limit (<= 0: never)
+  // rollouts (code objects built with -DDMC_ROLLOUT=1, which report it in
+  // dmc_rollout_caps).  A zero-filled block is a launch without them.
+  // DMC_FLAG_POLICY: the control of step t is an MLP over the observation (plus
+  // ctrl[t] with DMC_FLAG_CTRL).  Weights shared by the batch, packed per layer as
+  // W[out][in] row-major then b[out]: policy_nlayers (1 or 2) tanh layers of
+  // policy_width[l] units, then the linear output layer of NU units.
+  DMC_CREALPTR policy;
+  int policy_nlayers;
+  int policy_width[2];
+  // per-step outputs of the launch's step t, each optional (null: not stored):
+  DMC_REALPTR reward_out;  // [nenv] at reward_out + t*reward_out_st: reward of the state after step t
+  DMC_REALPTR obs_out;     // [nenv][NOBS] at obs_out + t*obs_out_st: its observation
+  DMC_REALPTR action_out;  // [nenv][NU] at action_out + t*action_out_st: the control applied at
+                           // step t, before the ctrlrange clamp and the bad-control check
+  long long reward_out_st, obs_out_st, action_out_st;
 };
 // bits of DmcArgs.flags
 #define DMC_FLAG_CTRL 1          // ctrl pointer valid (else reuse ctrl_store)
@@ -56,6 +71,7 @@ struct DmcArgs {
 #define DMC_FLAG_EPISODES 256      // dmc_step with outputs: skip envs with ep_done != 0, count ep_step, set ep_done;
                                    // dmc_init_episode: ep_step, ep_done and warn <- 0 for the envs it writes
 #define DMC_FLAG_ZERO_TIME 512     // dmc_step: store time = 0 for the envs it stepped (settle launches of a reset)
+#define DMC_FLAG_POLICY 1024       // dmc_step of a rollout build: controls from the MLP at `policy`
 // bits of ep_done (enum dmc_done_bit of the header)
 #define DMC_EP_DONE_LIMIT 1        // the episode reached step_limit
 #define DMC_EP_DONE_BAD_STATE 2    // a launch raised a warning bit (mjtWarning) for the env
@@ -85,3 +101,11 @@ static_assert(sizeof(DmcInfo) == 20*sizeof(int), "dmc_info is 20 ints");
 // code object honours.  A code object without the global, or with a bit clear
 // (team mode), makes the host refuse the entry points that need it.
 typedef int DmcEpisodeCaps;
+
+// `dmc_rollout_caps`: a third device global, exported by rollout builds only
+// (-DDMC_ROLLOUT=1, one env per lane): what dmc_batch_rollout may ask of the code
+// object.  Absent (read as 0) in every other build.
+typedef int DmcRolloutCaps;
+#define DMC_ROLLOUT_CAP_OUTPUTS 1         // per-step reward / observation / action stores
+#define DMC_ROLLOUT_CAP_POLICY 2          // DMC_FLAG_POLICY
+#define DMC_ROLLOUT_CAP_WIDTH_SHIFT 8     // caps >> 8: the widest hidden layer it takes

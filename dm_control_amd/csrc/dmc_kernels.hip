@@ -4821,6 +4821,239 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
   if (accumulate) a.episode_return[e] += rew;
 }
 
+#ifdef DMC_ROLLOUT
+// ---------------------------------------------------------------------------
+// Rollout builds (-DDMC_ROLLOUT=1, one env per lane): dmc_step additionally
+// stores every step's reward, observation and control (DmcArgs, "rollouts") and
+// can take the controls from an MLP over the observation (DMC_FLAG_POLICY).  An
+// env lives in one lane and so does its observation: the MLP is this lane's own
+// FMAs over weights whose addresses depend on kernel arguments and loop counters
+// only (wave-uniform: scalar loads).  A build without the define has none of this.
+// ---------------------------------------------------------------------------
+static_assert(!TEAMED, "DMC_ROLLOUT is built for the one-env-per-lane kernel, not for team mode");
+#ifndef DMC_POLICY_MAX_WIDTH
+#define DMC_POLICY_MAX_WIDTH 64
+#endif
+static_assert(DMC_POLICY_MAX_WIDTH >= 1 && DMC_POLICY_MAX_WIDTH < (1 << 20), "hidden width cap");
+// the first hidden vector of a two-layer policy has this lane's column of LDS
+// (a model without constraint rows has one wave's worth of words otherwise)
+constexpr int ROLLOUT_LDS_WORDS =
+    LDS_WORDS > LANES*DMC_POLICY_MAX_WIDTH ? LDS_WORDS : LANES*DMC_POLICY_MAX_WIDTH;
+constexpr bool ROLLOUT_OBS_STAGE_FITS = ROLLOUT_LDS_WORDS >= LANES*(NOBS > 0 ? NOBS : 1);
+constexpr DmcRolloutCaps ROLLOUT_CAPS = DMC_ROLLOUT_CAP_OUTPUTS | DMC_ROLLOUT_CAP_POLICY |
+                                        (DMC_POLICY_MAX_WIDTH << DMC_ROLLOUT_CAP_WIDTH_SHIFT);
+
+// act <- MLP(obs).  `col`: this lane's LDS column (word k at col[k*LANES]); the
+// constraint rows kept there are dead between steps.  One hidden layer is
+// streamed (per unit: a dot product, a tanh, NU FMAs into `act`; no hidden vector
+// is kept); of two, the first goes to `col` and the second is streamed over it.
+// The host checked the widths against the cap and the output width against NU.
+#ifdef DMC_HOST_SHIM
+typedef const real policy_word;
+#else
+// Nothing writes the weights while the kernel runs: read through the constant
+// address space, a load at a wave-uniform address is a scalar load (through a
+// plain pointer the compiler must assume one of the kernel's stores may alias it,
+// and issues a vector load of the same word in every lane).
+typedef const real __attribute__((address_space(4))) policy_word;
+#endif
+// One wave per SIMD has nothing to hide a scalar load's latency behind, and a loop
+// that loads a weight, waits and multiplies pays it once per weight (measured: the
+// 17-64-64-6 policy took 0.2 ms per step that way, five times the physics).  So a
+// layer is evaluated POLICY_UNITS units at a time, and a runtime fan-in in chunks of
+// POLICY_CHUNK inputs: the rows' loads are issued together and waited for once.  A
+// unit's sum still runs over its inputs in order.
+constexpr int POLICY_UNITS = 4, POLICY_CHUNK = 16;
+
+// x: the inputs in registers (fan-in FIN, a compile-time constant)
+template <int FIN> struct PolicyRegs {
+  const real* x;
+  template <int U> __device__ __forceinline__ void dots(policy_word* w, int, real* s) const {
+    DMC_UNROLL
+    for (int u = 0; u < U; u++)
+      DMC_UNROLL
+      for (int k = 0; k < FIN; k++) s[u] += w[u*FIN + k]*x[k];
+  }
+  __device__ __forceinline__ int fan_in() const { return FIN; }
+};
+// x: the inputs in this lane's LDS column (fan-in n, known at run time)
+struct PolicyColumn {
+  const real* col;
+  int n;
+  template <int U> __device__ __forceinline__ void dots(policy_word* w, int, real* s) const {
+    int k = 0;
+    for (; k + POLICY_CHUNK <= n; k += POLICY_CHUNK) {
+      real x[POLICY_CHUNK];
+      DMC_UNROLL
+      for (int c = 0; c < POLICY_CHUNK; c++) x[c] = col[(k + c)*LANES];
+      DMC_UNROLL
+      for (int u = 0; u < U; u++)
+        DMC_UNROLL
+        for (int c = 0; c < POLICY_CHUNK; c++) s[u] += w[u*n + k + c]*x[c];
+    }
+    for (; k < n; k++) {
+      const real x = col[k*LANES];
+      DMC_UNROLL
+      for (int u = 0; u < U; u++) s[u] += w[u*n + k]*x;
+    }
+  }
+  __device__ __forceinline__ int fan_in() const { return n; }
+};
+// h_j = tanh(b[j] + W[j] . x) for the `width` units of a layer, emit(j, U, h) for
+// every group of U consecutive units (POLICY_UNITS of them, then one at a time)
+template <class In, class Emit>
+DEV void policy_layer(policy_word* w, policy_word* b, int width, const In& in, Emit&& emit) {
+  const int n = in.fan_in();
+  int j = 0;
+  for (; j + POLICY_UNITS <= width; j += POLICY_UNITS) {
+    real h[POLICY_UNITS];
+    DMC_UNROLL
+    for (int u = 0; u < POLICY_UNITS; u++) h[u] = b[j + u];
+    in.template dots<POLICY_UNITS>(w + j*n, n, h);
+    DMC_UNROLL
+    for (int u = 0; u < POLICY_UNITS; u++) h[u] = tanh(h[u]);
+    emit(j, POLICY_UNITS, h);
+  }
+  for (; j < width; j++) {
+    real h[1] = {b[j]};
+    in.template dots<1>(w + j*n, n, h);
+    h[0] = tanh(h[0]);
+    emit(j, 1, h);
+  }
+}
+
+DEV void policy_mlp(const DmcArgs& a, const real* obs, real* act, real* col) {
+  policy_word* p = (policy_word*)a.policy;
+  const int w0 = a.policy_width[0];
+  policy_word* b0 = p + w0*NOBS;
+  const PolicyRegs<NOBS> first = {obs};
+  // the output layer, streamed: act += W[:, j..j+U) h
+  policy_word* wo;
+  int no;
+  const auto output = [&](int j, int U, const real* h) {
+    for (int u = 0; u < U; u++)
+      DMC_UNROLL
+      for (int i = 0; i < NU; i++) act[i] += wo[i*no + j + u]*h[u];
+  };
+  if (a.policy_nlayers == 1) {
+    wo = b0 + w0; no = w0;
+    policy_word* bo = wo + NU*w0;
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) act[i] = bo[i];
+    policy_layer(p, b0, w0, first, output);
+  } else {
+    const int n1 = a.policy_width[1];
+    policy_word* w1 = b0 + w0;
+    policy_word* b1 = w1 + n1*w0;
+    wo = b1 + n1; no = n1;
+    policy_word* bo = wo + NU*n1;
+    policy_layer(p, b0, w0, first, [&](int j, int U, const real* h) {
+      for (int u = 0; u < U; u++) col[(j + u)*LANES] = h[u];
+    });
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) act[i] = bo[i];
+    policy_layer(w1, b1, n1, PolicyColumn{col, w0}, output);
+  }
+}
+
+// the per-step outputs of the launch's step t: reward and observation of the state
+// after it (the observation transposed through LDS like write_outputs does, as
+// coalesced wave stores).  A rollout launch is lock-step: every lane with an env
+// is here, lanes 0..nvalid-1 of a partial last block.
+DEV void rollout_outputs(const DmcArgs& a, int e, int t, const real* obs, real rew,
+                         real* lds_base) {
+  if (a.reward_out) a.reward_out[(long long)t*a.reward_out_st + e] = rew;
+  if (!a.obs_out) return;
+  real* dst = a.obs_out + (long long)t*a.obs_out_st;
+  if (ROLLOUT_OBS_STAGE_FITS) {
+    const int lane = threadIdx.x;
+    DMC_UNROLL
+    for (int k = 0; k < NOBS; k++) lds_base[k*LANES + lane] = obs[k];
+    __syncthreads();
+    const long long base = (long long)blockIdx.x*blockDim.x;
+    const long long left = a.nenv - base;
+    const int nvalid = left < (long long)blockDim.x ? (int)left : (int)blockDim.x;
+    real* out = dst + base*NOBS;
+    for (int w = lane; w < nvalid*NOBS; w += nvalid)
+      out[w] = lds_base[(w % NOBS)*LANES + w/NOBS];
+    __syncthreads();      // (the next step writes its rows over these words)
+  } else {
+    DMC_UNROLL
+    for (int k = 0; k < NOBS; k++) dst[(long long)e*NOBS + k] = obs[k];
+  }
+}
+// The loop of a rollout launch reads its arguments from the kernarg segment again
+// where it needs them -- the controls at the top of a step, the records at its
+// bottom, the stores after the last step -- through a pointer the compiler cannot
+// trace back to the segment.  Loaded once at the kernel's entry they all stay in
+// SGPRs across physics_step, and with the policy's and the records' arguments the
+// unrolled cheetah and hopper builds go past the SGPR spill budget of their tier
+// (169 and 186 against 128).  DMC_LATE_ARGS(x): `x` is the argument block, read late.
+#ifdef DMC_HOST_SHIM
+#define DMC_LATE_ARGS(x) const DmcArgs& x = a
+#else
+#define DMC_LATE_ARGS(x) DmcArgs x; late_copy(x)
+// every member of the block (it is the kernel's one parameter: it starts the
+// segment), member by member: the compiler keeps the ones that are used, as scalars
+#define DMC_LATE(m) d.m = s->m
+DEV void late_copy(DmcArgs& d) {
+  const __attribute__((address_space(4))) DmcArgs* s =
+      (const __attribute__((address_space(4))) DmcArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(s));
+  DMC_LATE(nenv); DMC_LATE(nsub); DMC_LATE(flags); DMC_LATE(task_param_i); DMC_LATE(seed);
+  DMC_LATE(qpos); DMC_LATE(qvel); DMC_LATE(warm); DMC_LATE(time);
+  DMC_LATE(ctrl); DMC_LATE(ctrl_sk); DMC_LATE(ctrl_se); DMC_LATE(ctrl_store);
+  DMC_LATE(obs); DMC_LATE(obs_sk); DMC_LATE(obs_se); DMC_LATE(reward);
+  DMC_LATE(episode_return); DMC_LATE(sensordata); DMC_LATE(xpos); DMC_LATE(xmat);
+  DMC_LATE(qacc); DMC_LATE(warn); DMC_LATE(stats); DMC_LATE(ws); DMC_LATE(taskdata);
+  for (int k = 0; k < 4; k++) DMC_LATE(task_param_r[k]);
+  DMC_LATE(modelparam); DMC_LATE(nsteps); DMC_LATE(ctrl_st);
+  DMC_LATE(env_mask); DMC_LATE(ep_step); DMC_LATE(ep_done); DMC_LATE(step_limit);
+  DMC_LATE(policy); DMC_LATE(policy_nlayers);
+  for (int k = 0; k < 2; k++) DMC_LATE(policy_width[k]);
+  DMC_LATE(reward_out); DMC_LATE(obs_out); DMC_LATE(action_out);
+  DMC_LATE(reward_out_st); DMC_LATE(obs_out_st); DMC_LATE(action_out_st);
+}
+#undef DMC_LATE
+static_assert(sizeof(DmcArgs) == 352, "late_copy names every member of DmcArgs");
+#endif
+
+// control of the launch's step t: pi(o_t) if there is a policy, plus ctrl[t] if given
+// (a NaN / inf sum: mj_fwdActuation's ctrl check, warn and zero the controls); with
+// neither, the held control
+template <class EnvT>
+DEV void rollout_control(EnvT& E, const DmcArgs& a, int e, int t, const real* obs, real* col) {
+  const bool policy = (a.flags & DMC_FLAG_POLICY) != 0;
+  if (a.flags & (DMC_FLAG_POLICY | DMC_FLAG_CTRL)) {
+    real act[NU > 0 ? NU : 1];
+    if (policy) policy_mlp(a, obs, act, col);
+    if (a.flags & DMC_FLAG_CTRL) {
+      const real* ctrl = a.ctrl + (long long)t*a.ctrl_st;
+      DMC_UNROLL
+      for (int i = 0; i < NU; i++) {
+        const real c = ctrl[i*a.ctrl_sk + (long long)e*a.ctrl_se];
+        act[i] = policy ? act[i] + c : c;
+      }
+    }
+    bool bc = false;
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) {
+      if (a.action_out) a.action_out[(long long)t*a.action_out_st + (long long)e*NU + i] = act[i];
+      E.ctrl[i] = act[i];
+      bc |= bad(act[i]);
+    }
+    if (bc) {
+      E.warn |= WARN_BADCTRL;
+      DMC_UNROLL
+      for (int i = 0; i < NU; i++) E.ctrl[i] = 0;
+    }
+  } else if (t == 0) {
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) E.ctrl[i] = a.ctrl_store[(long long)i*a.nenv + e];
+  }
+}
+#endif  // DMC_ROLLOUT
+
 // nsteps x (nsub x Physics.step, then observation + reward of the new state).
 // flags bit0: ctrl given (else reuse ctrl_store); bit1: skip outputs (settle)
 //
@@ -4853,7 +5086,11 @@ dmc_step(DmcArgs a) {
   Env E;
   real time;
   const long long n = a.nenv;
+#ifdef DMC_ROLLOUT
+  __shared__ real lds_rows[ROLLOUT_LDS_WORDS];
+#else
   __shared__ real lds_rows[TEAMED ? TEAM_LDS_WORDS*(LANES/TEAM) : LDS_WORDS];
+#endif
   const Work W = TEAMED
       ? Work{lds_rows + (threadIdx.x/TEAM)*TEAM_LDS_WORDS, a.ws + (long long)e*WS_WORDS, 1}
       : Work{lds_rows + threadIdx.x, a.ws + e, n};
@@ -4867,10 +5104,28 @@ dmc_step(DmcArgs a) {
   const bool frames = !(TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0 && !a.xpos && !a.xmat);
   real ret = 0;               // register copy of the episode return
   if (!TEAMED && outputs) ret = a.episode_return[e];
+#ifdef DMC_ROLLOUT
+  // the observation and reward of the state after the step just taken: computed at
+  // the bottom of every iteration (the one call site of the task layer in this
+  // build), read by the policy at the top of the next one and by the stores after
+  // the loop -- never live across physics_step.  o_0 is the batch's current one.
+  real robs[NOBS > 0 ? NOBS : 1];
+  real rrew = 0;
+  if (a.flags & DMC_FLAG_POLICY) {
+    DMC_UNROLL
+    for (int k = 0; k < NOBS; k++) robs[k] = a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se];
+  }
+#endif
 #ifdef DMC_STEP_PROFILE
   const long long tk_ = wall_clock64();
 #endif
   for (int t = 0; t < nsteps; t++) {
+#ifdef DMC_ROLLOUT
+    {
+      DMC_LATE_ARGS(at);
+      rollout_control(E, at, e, t, robs, lds_rows + threadIdx.x);
+    }
+#else
     if (TEAMED) {
       // (a lane applies the actuators i = lane mod TEAM: it fetches those controls)
       const int tl = tlane();
@@ -4902,6 +5157,7 @@ dmc_step(DmcArgs a) {
       DMC_UNROLL
       for (int i = 0; i < NU; i++) E.ctrl[i] = a.ctrl_store[i*n + e];
     }
+#endif
     for (int s = 0; s < a.nsub; s++)
       physics_step(E, W, time, tol, t == 0 && s == 0 && (a.flags & DMC_FLAG_STALE_FIRST));
     if (outputs) {
@@ -4909,17 +5165,35 @@ dmc_step(DmcArgs a) {
       if (!frames) check_state(E, time);
       else observe_stage(E, time);
 #endif
+#ifdef DMC_ROLLOUT
+      {
+        DMC_LATE_ARGS(ab);
+        rrew = task_outputs(E, ab, robs);
+        ret += rrew;
+        rollout_outputs(ab, e, t, robs, rrew, lds_rows);
+      }
+#else
       if (TEAMED) store_outputs(E, a, e, true, lds_rows);
       else if (t < nsteps - 1) {    // a step nobody observes: its reward alone is kept
         real obs[NOBS > 0 ? NOBS : 1];
         ret += task_outputs(E, a, obs);
       }
+#endif
     }
   }
 #ifdef DMC_STEP_PROFILE
   E.prof[7] = (real)(wall_clock64() - tk_);      // all substeps
 #endif
+#ifdef DMC_ROLLOUT
+  {
+  DMC_LATE_ARGS(a_end);
+  const DmcArgs& a = a_end;       // (shadows the parameter down to the end of the kernel)
+#endif
+#ifdef DMC_ROLLOUT
+  if (a.flags & (DMC_FLAG_CTRL | DMC_FLAG_POLICY)) {
+#else
   if (!TEAMED && (a.flags & DMC_FLAG_CTRL)) {      // data.ctrl: the controls of the last step
+#endif
     DMC_UNROLL
     for (int i = 0; i < NU; i++) a.ctrl_store[i*n + e] = E.ctrl[i];
   }
@@ -4927,6 +5201,12 @@ dmc_step(DmcArgs a) {
     DMC_UNROLL
     for (int i = 0; i < NV; i++) a.qacc[i*n + e] = E.qacc[i];
   }
+#ifdef DMC_ROLLOUT
+  if (outputs) {                 // the last step's outputs, as the loop left them
+    write_outputs(E, a, e, robs, rrew, lds_rows, live);
+    a.episode_return[e] = ret;
+  }
+#else
   if (!TEAMED && outputs) {      // the last step's outputs
     real obs[NOBS > 0 ? NOBS : 1];
     const real rew = task_outputs(E, a, obs);
@@ -4934,6 +5214,7 @@ dmc_step(DmcArgs a) {
     write_outputs(E, a, e, obs, rew, lds_rows, live);
     a.episode_return[e] = ret;
   }
+#endif
 #ifdef DMC_SOLVER_PROFILE
   __syncthreads();
   for (int k = 0; k < 8 && k < NOBS; k++) a.obs[(long long)e*a.obs_se + k] = E.prof[k];
@@ -4944,6 +5225,9 @@ dmc_step(DmcArgs a) {
   if (EPISODE_CAPS && (a.flags & DMC_FLAG_ZERO_TIME)) time = 0;
   store_env(E, a, e, time);
   if (counts_episodes(a)) count_episode_step(a, e, E.warn);
+#ifdef DMC_ROLLOUT
+  }
+#endif
 }
 
 // observation / reward / sensors of the current state (reset, after_reset)
@@ -5121,4 +5405,7 @@ extern "C" __device__ const DmcInfo dmc_info = {
     .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA, .threads_per_block = LANES,
     .nmodelparam = DMC_NMODELPARAM, .seq_launch = TEAMED ? 0 : 1};
 extern "C" __device__ const DmcEpisodeCaps dmc_episode_caps = EPISODE_CAPS;
+#ifdef DMC_ROLLOUT
+extern "C" __device__ const DmcRolloutCaps dmc_rollout_caps = ROLLOUT_CAPS;
+#endif
 #endif

@@ -409,8 +409,18 @@ class Physics(_control.Physics):
   _GROUP = 64                 # lanes per env of build mode "coop" (128: two wavefronts)
 
   def __init__(self, model, batch_size=None, device=0, precision='f32',
-               task=None, ncon_max=None, build_mode=None, group=None, per_env=()):
+               task=None, ncon_max=None, build_mode=None, group=None, per_env=(),
+               rollout=False):
+    """rollout: build the rollout variant of the one-env-per-lane kernel
+    (`rollout_device`, `VecEnv.rollout`): whatever the batch size, the
+    several-lanes kernel is not selected."""
     self.model = model
+    self._rollout = bool(rollout)
+    if self._rollout and (build_mode or self._BUILD_MODE) in ('coop', 'team'):
+      raise ValueError(
+          'rollout=True runs on the one-env-per-lane kernel; this model is built for '
+          'build mode %r (the humanoid and soccer have no rollout build)'
+          % (build_mode or self._BUILD_MODE))
     self._params = model_params.ModelParams(
         model, per_env, 1 if batch_size is None else int(batch_size))
     self._squeeze = batch_size is None
@@ -428,7 +438,8 @@ class Physics(_control.Physics):
     self._profile_calls = 0
     self._build_mode = build_mode or self._BUILD_MODE
     self._group = group or self._GROUP
-    if build_mode is None and self._build_mode == 'auto' and precision != 'mixed':
+    if (build_mode is None and self._build_mode == 'auto' and precision != 'mixed'
+        and not self._rollout):
       policy = self._COOP_POLICY
       if precision == 'f64' and self._COOP_POLICY_F64 is not None:
         policy = self._COOP_POLICY_F64
@@ -439,7 +450,7 @@ class Physics(_control.Physics):
     path = build.build_model(
         model, self._task_id, precision, ncon_max, mode=self._build_mode,
         lds_budget=build.lds_budget_for(self._batch_size), group=self._group,
-        per_env=self._params.per_env)
+        per_env=self._params.per_env, rollout=self._rollout)
     self._code_object = path
     self._hip_model = wrapper.HipModel(path, device)
     self._batch = wrapper.HipBatch(self._hip_model, self._batch_size)
@@ -580,6 +591,32 @@ class Physics(_control.Physics):
     if check:
       self.check_invalid_state()
 
+  def rollout_device(self, nsteps, n_sub_steps=1, ctrl=None, policy=None, obs_out=None,
+                     reward_out=None, action_out=None):
+    """`nsteps` control steps of `n_sub_steps` substeps in one launch per chunk
+    (`dmc_batch_rollout`; a `Physics(..., rollout=True)`), over device memory of
+    this batch's dtype.  The control of step t is policy(o_t) if `policy` is given,
+    plus ctrl[t] if `ctrl` is given; o_0 is the current observation.
+
+    ctrl: None or (ptr, stride_k, stride_env, stride_t) in elements; policy: None
+    or (ptr, widths): the packed weights (`rl.policy.MLPPolicy.packed`) and the
+    hidden widths followed by the output width; obs_out / reward_out /
+    action_out: None or (ptr, stride_t): [nsteps, B, nobs], [nsteps, B], [nsteps, B, nu]
+    written per step.  The fields afterwards hold the last step's outputs."""
+    if not self._rollout:
+      raise ValueError('rollout_device needs Physics(..., rollout=True)')
+    if policy is not None:
+      self._ensure_outputs()       # o_0: the observation of the current state
+    if self._profiling:
+      self._batch.timer_start()
+    self._batch.rollout(nsteps, n_sub_steps, ctrl, policy, reward_out, obs_out, action_out)
+    if self._profiling:
+      ms, _ = self._batch.timer_stop()
+      self._profile_seconds += ms*1e-3
+      self._profile_calls += n_sub_steps*nsteps
+    self._pending_ctrl = None
+    self._dirty = False
+
   def forward(self, count_contacts=False):
     """Recomputes derived quantities (observation inputs) without stepping."""
     self._batch.forward(count_contacts)
@@ -704,7 +741,8 @@ class Physics(_control.Physics):
     Physics.__init__(new, self.model,
                      None if self._squeeze else self._batch_size,
                      self._device, self._precision, self._task_id,
-                     self._ncon_max, self._build_mode, self._group, self._params.per_env)
+                     self._ncon_max, self._build_mode, self._group, self._params.per_env,
+                     self._rollout)
     new._batch.copy_state_from(self._batch)
     for name, v in self._params.values.items():
       new._params.values[name][...] = v

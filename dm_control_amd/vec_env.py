@@ -39,8 +39,10 @@ class VecEnv:
   def __init__(self, domain_name, task_name, num_envs, seed=None,
                device=0, precision='f32', torch_io=False, task_kwargs=None,
                environment_kwargs=None, per_env=(), per_env_episodes=False,
-               episode_offsets=None):
-    """per_env_episodes: every env ends and restarts its episodes on its own
+               episode_offsets=None, rollout=False):
+    """rollout: build the rollout variant of the step kernel, for `rollout()`
+    (torch mode, lock-step episodes, one-env-per-lane domains).
+    per_env_episodes: every env ends and restarts its episodes on its own
     (needs device_init, the default of torch mode).  episode_offsets: None,
     'staggered' (env e starts e/B of the way into its first episode) or int [B]:
     the step count every env's first episode starts with after `reset()`."""
@@ -49,6 +51,15 @@ class VecEnv:
       env_kw['per_env'] = tuple(per_env)
     env_kw.update(batch_size=int(num_envs), device=device,
                   precision=precision, flat_observation=True)
+    self._rollout = bool(rollout or env_kw.get('rollout'))
+    if self._rollout:
+      if not torch_io:
+        raise ValueError('rollout=True needs torch_io=True: a rollout records into '
+                         'CUDA tensors')
+      if per_env_episodes:
+        raise ValueError('rollout=True is lock-step: not with per_env_episodes=True')
+      env_kw['rollout'] = True
+      self._policy_cache = {}
     env_kw.setdefault('device_init', bool(torch_io))
     task_kw = dict(task_kwargs or {})
     task_kw.setdefault('random', seed)
@@ -195,6 +206,75 @@ class VecEnv:
     else:
       obs = self._obs_t.clone()
     return obs, rewards, dones, infos
+
+  # -- rollouts -------------------------------------------------------------------
+  def _policy_device(self, policy):
+    """(device pointer, widths) of `policy`: uploaded once per policy object and
+    again after its `update_`."""
+    import torch
+    if policy.obs_dim != self.observation_dim or policy.action_dim != self.action_dim:
+      raise ValueError('the policy maps %d -> %d values, the env %d -> %d'
+                       % (policy.obs_dim, policy.action_dim, self.observation_dim,
+                          self.action_dim))
+    held = self._policy_cache.get(id(policy))
+    if held is None or held[0] is not policy or held[1] != policy.version:
+      flat = torch.from_numpy(policy.packed(self._physics.dtype)).to(self._obs_t.device)
+      held = (policy, policy.version, flat)
+      self._policy_cache[id(policy)] = held
+    return held[2].data_ptr(), policy.widths
+
+  def rollout(self, T, policy=None, actions=None, noise=None):
+    """Up to `T` control steps in one kernel launch per 64 steps, no host round
+    trip in between (`VecEnv(..., torch_io=True, rollout=True)`).
+
+    policy: an `rl.policy.MLPPolicy`, evaluated by the step kernel on each env's
+    observation: a_t = policy(o_t) + noise[t], `noise` an optional CUDA tensor
+    [T, B, nu].  Without a policy, `actions` [T, B, nu] is the action sequence
+    (open loop).  Runs n = min(T, steps left in the episode) steps and returns a
+    dict of CUDA tensors: obs [n, B, D] (obs[t]: the observation after step t),
+    actions [n, B, nu], rewards [n, B], dones [n, B] (the last row true when the
+    time limit was reached), next_obs [B, D] (what to act on next: after a reset
+    the new episode's first observation) and, when the episode ended,
+    terminal_observation [B, D]."""
+    import torch
+    if not self._rollout:
+      raise ValueError('rollout() needs VecEnv(..., torch_io=True, rollout=True)')
+    if (policy is None) == (actions is None):
+      raise ValueError('pass either a policy (closed loop) or actions (open loop)')
+    if noise is not None and policy is None:
+      raise ValueError('noise is added to a policy; without one pass `actions`')
+    left = self._step_limit - self._count
+    n = int(T) if math.isinf(left) else int(min(int(T), max(1, math.ceil(left))))
+    if n < 1:
+      raise ValueError('T must be at least 1')
+    B, D, nu = self.num_envs, self.observation_dim, self.action_dim
+    dtype, dev = self._obs_t.dtype, self._obs_t.device
+    ctrl = None
+    seq = actions if policy is None else noise
+    if seq is not None:
+      if not seq.is_cuda or seq.dim() != 3 or seq.shape[0] < n or seq.shape[1:] != (B, nu):
+        raise ValueError('expected a CUDA tensor [>= %d, %d, %d]' % (n, B, nu))
+      seq = seq[:n].to(dtype).contiguous()
+      ctrl = (seq.data_ptr(), 1, nu, B*nu)
+    out = {'obs': torch.empty(n, B, D, dtype=dtype, device=dev),
+           'actions': torch.empty(n, B, nu, dtype=dtype, device=dev),
+           'rewards': torch.empty(n, B, dtype=dtype, device=dev)}
+    self._physics.rollout_device(
+        n, self._nsub, ctrl=ctrl,
+        policy=None if policy is None else self._policy_device(policy),
+        obs_out=(out['obs'].data_ptr(), B*D), reward_out=(out['rewards'].data_ptr(), B),
+        action_out=(out['actions'].data_ptr(), B*nu))
+    self._keepalive = seq
+    self._count += n
+    done = self._count >= self._step_limit
+    out['dones'] = torch.zeros(n, B, dtype=torch.bool, device=dev)
+    if done:
+      out['dones'][-1] = True
+      out['terminal_observation'] = self._obs_t.clone()
+      out['next_obs'] = self._reset_torch()
+    else:
+      out['next_obs'] = self._obs_t.clone()
+    return out
 
   def close(self):
     self._physics.free()

@@ -65,9 +65,24 @@ class ModelInfo(ctypes.Structure):
       'nmodelparam', 'seq_launch')]
 
 
-# every symbol declared in include/dmc_hip.h: (restype, argtypes)
 _vp, _ci, _cll, _cs = (ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong,
                        ctypes.c_size_t)
+
+# enum dmc_rollout_cap
+ROLLOUT_OUTPUTS, ROLLOUT_POLICY, ROLLOUT_WIDTH_SHIFT = 1, 2, 8
+
+
+class Rollout(ctypes.Structure):
+  """struct dmc_rollout."""
+  _fields_ = [('nsteps', _ci), ('nsub', _ci), ('ctrl', _vp),
+              ('ctrl_stride_k', _cll), ('ctrl_stride_env', _cll), ('ctrl_stride_t', _cll),
+              ('policy', _vp), ('nlayers', _ci), ('width', _ci*3),
+              ('reward_out', _vp), ('reward_stride_t', _cll),
+              ('obs_out', _vp), ('obs_stride_t', _cll),
+              ('action_out', _vp), ('action_stride_t', _cll)]
+
+
+# every symbol declared in include/dmc_hip.h: (restype, argtypes)
 SIGNATURES = {
     'dmc_version': (_ci, []),
     'dmc_last_error': (ctypes.c_char_p, []),
@@ -94,6 +109,8 @@ SIGNATURES = {
     'dmc_batch_forward': (_ci, [_vp, _ci]),
     'dmc_batch_step': (_ci, [_vp, _vp, _cll, _cll, _ci, _ci, _ci]),
     'dmc_batch_step_n': (_ci, [_vp, _vp, _cll, _cll, _cll, _ci, _ci, _ci]),
+    'dmc_model_rollout_caps': (_ci, [_vp]),
+    'dmc_batch_rollout': (_ci, [_vp, ctypes.POINTER(Rollout)]),
     'dmc_batch_read': (_ci, [_vp, _ci, _vp, _cs]),
     'dmc_batch_field_bytes': (_cs, [_vp, _ci]),
     'dmc_batch_device_ptr': (_vp, [_vp, _ci]),
@@ -197,6 +214,12 @@ class HipModel:
     _check(self._lib.dmc_model_get_info(self.ptr, ctypes.byref(self.info)))
     self.device_id = device_id
     self.dtype = np.float32 if self.info.real_size == 4 else np.float64
+
+  @property
+  def rollout_caps(self):
+    """ROLLOUT_* bits and, above ROLLOUT_WIDTH_SHIFT, the widest hidden layer of
+    a device policy; 0: not a rollout build (`build_model(..., rollout=True)`)."""
+    return self._lib.dmc_model_rollout_caps(self.ptr)
 
   @classmethod
   def from_code(cls, code, device_id=0):
@@ -331,6 +354,30 @@ class HipBatch:
     """`nsteps` control steps; step t reads ctrl_ptr + t*stride_t reals."""
     _check(self._lib.dmc_batch_step_n(self.ptr, ctrl_ptr, stride_k, stride_env,
                                       stride_t, nsteps, nsub, int(want_outputs)))
+
+  def rollout(self, nsteps, nsub=1, ctrl=None, policy=None, reward_out=None,
+              obs_out=None, action_out=None):
+    """`dmc_batch_rollout` over device memory of the batch's real type.
+
+    ctrl: None or (ptr, stride_k, stride_env, stride_t), in reals; policy: None
+    or (ptr, widths) with widths = hidden widths then the output width (nu), the
+    weights packed as `rl.policy.MLPPolicy.packed` lays them out; *_out: None or
+    (ptr, stride_t): [nsteps][nenv], [nsteps][nenv][nobs], [nsteps][nenv][nu]."""
+    r = Rollout()
+    r.nsteps, r.nsub = int(nsteps), int(nsub)
+    if ctrl is not None:
+      r.ctrl, r.ctrl_stride_k, r.ctrl_stride_env, r.ctrl_stride_t = ctrl
+    if policy is not None:
+      ptr, widths = policy
+      widths = [int(w) for w in widths]
+      r.policy, r.nlayers = ptr, len(widths) - 1
+      for l, w in enumerate(widths[:3]):
+        r.width[l] = w
+    for name, out in (('reward', reward_out), ('obs', obs_out), ('action', action_out)):
+      if out is not None:
+        setattr(r, name + '_out', out[0])
+        setattr(r, name + '_stride_t', out[1])
+    _check(self._lib.dmc_batch_rollout(self.ptr, ctypes.byref(r)))
 
   # -- per-env episodes --------------------------------------------------------
   def episodes_enable(self, step_limit=0):

@@ -102,7 +102,9 @@ typedef struct dmc_model_info {
  * struct)
  * 102: dmc_model_info gained `seq_launch` at its end (same rule)
  * 103: per-env episodes (dmc_batch_episodes_enable ... dmc_batch_set_masked, DMC_STEP_ZERO_TIME);
- *      code objects export `dmc_episode_caps`; older ones still load and step */
+ *      code objects export `dmc_episode_caps`; older ones still load and step
+ * 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout); rollout builds export
+ *      `dmc_rollout_caps`, every other code object loads and steps as before */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
@@ -255,6 +257,55 @@ int dmc_batch_episode_read(dmc_batch* batch, int which, int* dst, size_t bytes);
 int dmc_batch_episode_write(dmc_batch* batch, int which, const int* src, size_t bytes);
 int dmc_batch_mask_from_done(dmc_batch* batch);
 int dmc_batch_set_masked(dmc_batch* batch, int on);
+
+/* Rollouts (version 104): T control steps in one launch per chunk of at most
+ * DMC_SEQ_LAUNCH_MAX_STEPS, with every step's reward, observation and control
+ * recorded, and optionally the controls computed on the device by an MLP over the
+ * observation.  Needs a code object built as a rollout build of the
+ * one-env-per-lane kernel (build.build_model(..., rollout=True)); its capability
+ * word is dmc_model_rollout_caps (0: the code object takes no rollouts).
+ *
+ * Control of step t = policy(o_t) if `policy` is given, plus ctrl[t] if `ctrl` is
+ * given (the exploration term of a closed-loop rollout, or the whole action of an
+ * open-loop one); with neither, the held control.  o_0 is DMC_FIELD_OBS as the
+ * batch holds it, o_t the observation after step t-1.  A NaN / inf control raises
+ * DMC_WARN_BADCTRL and is applied as zeros, like a loaded one.
+ *
+ * policy: device memory, elements of the code object's real type, shared by the
+ * batch: per layer W[out][in] row-major then b[out]; `nlayers` (1 or 2) tanh layers
+ * of width[l] units (each <= the cap in the capability word), then a linear layer
+ * of width[nlayers] units, which must be the model's nu.
+ * Outputs (device memory, each may be NULL; strides in reals between steps):
+ *   reward_out + t*reward_stride_t   [nenv]        reward of the state after step t
+ *   obs_out    + t*obs_stride_t      [nenv][nobs]  its observation
+ *   action_out + t*action_stride_t   [nenv][nu]    the control of step t, before the
+ *                                                  ctrlrange clamp and the bad-control check
+ *                                                  (not written when the held control is used)
+ * The fields afterwards are those of `nsteps` calls of dmc_batch_step (the last
+ * step's outputs, DMC_FIELD_RETURN with every reward added); one call of T steps
+ * equals T calls of one step bit for bit.  Lock-step only: refused for a batch with
+ * per-env episodes enabled or an env mask set.  The batch timer counts control steps. */
+enum dmc_rollout_cap {
+  DMC_ROLLOUT_OUTPUTS = 1,        /* per-step outputs */
+  DMC_ROLLOUT_POLICY = 2,         /* device MLP policy */
+  DMC_ROLLOUT_WIDTH_SHIFT = 8     /* caps >> 8: the widest hidden layer */
+};
+typedef struct dmc_rollout {
+  int nsteps, nsub;
+  const void* ctrl;               /* element (t, k, env) at ctrl[t*ctrl_stride_t + k*ctrl_stride_k
+                                     + env*ctrl_stride_env]; NULL: none */
+  long long ctrl_stride_k, ctrl_stride_env, ctrl_stride_t;
+  const void* policy;             /* NULL: no policy */
+  int nlayers, width[3];          /* hidden widths, then width[nlayers] = the output width */
+  void* reward_out;
+  long long reward_stride_t;
+  void* obs_out;
+  long long obs_stride_t;
+  void* action_out;
+  long long action_stride_t;
+} dmc_rollout;
+int dmc_model_rollout_caps(const dmc_model* model);
+int dmc_batch_rollout(dmc_batch* batch, const dmc_rollout* rollout);
 
 /* timing of the step kernel on the batch's own stream (HIP events around the
  * launches issued since dmc_batch_timer_start); returns accumulated device
