@@ -1,8 +1,9 @@
 // dmc_api.cpp -- host runtime behind the C ABI of include/dmc_hip.h.
 //
 // Owns: the HIP module of a model-specialised code object, the HBM-resident
-// struct-of-arrays state of a batch, one HIP stream per batch, and the launch
-// of the step / observe / init kernels.  No torch types, no CPU fallback: if
+// struct-of-arrays state of a batch, one HIP stream per batch (and the side stream
+// and shadow buffers of an episode prefetch), and the launch of the step / observe /
+// init kernels.  No torch types, no CPU fallback: if
 // HIP or the code object is unavailable every call fails with a message.
 //
 // Reference counterparts: wrapper/core.py (MjModel :444-627, MjData :630-776,
@@ -85,6 +86,21 @@ struct dmc_batch {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false;
   long long launches = 0;
+  size_t ws_bytes = 0;
+  // episode prefetch (dmc_batch_episode_prefetch): the request, and what its first
+  // issue allocates -- side stream, events, shadow fields and shadow workspace
+  struct Prefetch {
+    enum State { NONE, PENDING, ISSUED } state = NONE;
+    uint64_t seed = 0;
+    int nsub = 0, step_flags = 0;
+    long long after_steps = 0, issued = 0;   // control steps: asked for, seen since the request
+    bool qacc = false;                       // the settle launch stored DMC_FIELD_QACC
+    hipStream_t side = nullptr;
+    hipEvent_t ready = nullptr;    // on the batch's stream: what the issue is ordered behind
+    hipEvent_t done = nullptr;     // on the side stream: the shadows are complete
+    void* field[DMC_FIELD_COUNT] = {};
+    void* ws = nullptr;
+  } prefetch;
 };
 
 namespace {
@@ -135,7 +151,7 @@ bool flipped(const dmc_batch* b, int f) {
 
 enum Shape { TASK_SETUP, MODEL_SHAPED };
 
-int launch(dmc_batch* b, hipFunction_t fn, DmcArgs& args, Shape shape) {
+int launch_on(dmc_batch* b, hipStream_t stream, hipFunction_t fn, DmcArgs& args, Shape shape) {
   size_t size = sizeof(DmcArgs);
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args,
                     HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
@@ -150,9 +166,13 @@ int launch(dmc_batch* b, hipFunction_t fn, DmcArgs& args, Shape shape) {
     block = (unsigned)(mi.lanes_per_env*mi.envs_per_block);
   }
   const unsigned grid = (unsigned)((b->nenv + per_block - 1)/per_block);
-  HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, b->stream,
+  HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, stream,
                                 nullptr, config));
   return 0;
+}
+
+int launch(dmc_batch* b, hipFunction_t fn, DmcArgs& args, Shape shape) {
+  return launch_on(b, b->stream, fn, args, shape);
 }
 
 // [rows][n] <-> [n][rows] on the host (elements of `elem` bytes), see `flipped`
@@ -221,6 +241,122 @@ int episode_array(const dmc_batch* b, int which, size_t bytes, const char* who) 
   return 0;
 }
 
+// -- episode prefetch ----------------------------------------------------------
+// Every field that dmc_init_episode or a dmc_step without outputs writes (load_env /
+// store_env and the tail of dmc_step in the kernel sources): what a prefetch shadows
+// and a take copies back.  The workspace is shadowed whole: overflow rows of two
+// concurrent launches must not collide, and a `mixed` build keeps the low words of
+// its state there.
+constexpr dmc_field SHADOWED[] = {
+    DMC_FIELD_QPOS, DMC_FIELD_QVEL, DMC_FIELD_WARMSTART, DMC_FIELD_TIME, DMC_FIELD_CTRL,
+    DMC_FIELD_QACC, DMC_FIELD_WARN, DMC_FIELD_STATS, DMC_FIELD_RETURN, DMC_FIELD_TASKDATA};
+
+void prefetch_free(dmc_batch* b) {
+  dmc_batch::Prefetch& p = b->prefetch;
+  if (p.side) (void)hipStreamSynchronize(p.side);
+  for (dmc_field f : SHADOWED)
+    if (p.field[f]) (void)hipFree(p.field[f]);
+  if (p.ws) (void)hipFree(p.ws);
+  if (p.ready) (void)hipEventDestroy(p.ready);
+  if (p.done) (void)hipEventDestroy(p.done);
+  if (p.side) (void)hipStreamDestroy(p.side);
+  p = dmc_batch::Prefetch();
+}
+
+// forgets the request; a prefetch that may still run (an issued one, or one that a
+// take declined) is waited for first, so that the caller may change what it reads
+int prefetch_drop(dmc_batch* b) {
+  dmc_batch::Prefetch& p = b->prefetch;
+  p.state = p.NONE;
+  if (p.side) {
+    HIP_TRY(hipSetDevice(b->model->device));
+    HIP_TRY(hipStreamSynchronize(p.side));
+  }
+  return 0;
+}
+
+// side stream, events, shadows (`ws` last: it tells that all of them exist)
+int prefetch_alloc(dmc_batch* b) {
+  dmc_batch::Prefetch& p = b->prefetch;
+  // the lowest priority: a step launch is never queued behind the settle
+  int least = 0, greatest = 0;
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+  HIP_TRY(hipStreamCreateWithPriority(&p.side, hipStreamNonBlocking, least));
+  HIP_TRY(hipEventCreateWithFlags(&p.ready, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
+  for (dmc_field f : SHADOWED) {
+    HIP_TRY(hipMalloc(&p.field[f], b->bytes[f]));
+    HIP_TRY(hipMemsetAsync(p.field[f], 0, b->bytes[f], p.side));
+  }
+  void* ws = nullptr;
+  HIP_TRY(hipMalloc(&ws, b->ws_bytes));
+  p.ws = ws;
+  HIP_TRY(hipMemsetAsync(p.ws, 0, b->ws_bytes, p.side));
+  return 0;
+}
+
+// what a whole-batch reset launches, on the side stream into the shadows
+int prefetch_issue(dmc_batch* b) {
+  dmc_batch::Prefetch& p = b->prefetch;
+  HIP_TRY(hipSetDevice(b->model->device));
+  if (!p.ws && prefetch_alloc(b)) {
+    prefetch_free(b);
+    return -1;
+  }
+  // behind what the batch's stream holds now: the steps counted by `after_steps`,
+  // a take that still copies from the shadows, launches that write the task data
+  HIP_TRY(hipEventRecord(p.ready, b->stream));
+  HIP_TRY(hipStreamWaitEvent(p.side, p.ready, 0));
+  HIP_TRY(hipMemcpyAsync(p.field[DMC_FIELD_TASKDATA], b->field[DMC_FIELD_TASKDATA],
+                         b->bytes[DMC_FIELD_TASKDATA], hipMemcpyDeviceToDevice, p.side));
+  DmcArgs a;
+  fill_args(b, a);   // (neither masked nor per-env episodes: the request was refused then)
+  a.qpos = p.field[DMC_FIELD_QPOS];
+  a.qvel = p.field[DMC_FIELD_QVEL];
+  a.warm = p.field[DMC_FIELD_WARMSTART];
+  a.time = p.field[DMC_FIELD_TIME];
+  a.ctrl_store = p.field[DMC_FIELD_CTRL];
+  a.episode_return = p.field[DMC_FIELD_RETURN];
+  a.taskdata = p.field[DMC_FIELD_TASKDATA];
+  a.warn = (unsigned*)p.field[DMC_FIELD_WARN];
+  a.stats = (int*)p.field[DMC_FIELD_STATS];
+  a.ws = p.ws;
+  p.qacc = b->aux_outputs;
+  a.qacc = p.qacc ? p.field[DMC_FIELD_QACC] : nullptr;
+  a.xpos = a.xmat = nullptr;      // (outputs: none of these launches writes them)
+  DmcArgs reset = a;              // dmc_batch_reset
+  reset.flags = DMC_FLAG_RESET_ONLY;
+  if (launch_on(b, p.side, b->model->k_init, reset, TASK_SETUP)) return -1;
+  HIP_TRY(hipMemsetAsync(p.field[DMC_FIELD_WARN], 0, b->bytes[DMC_FIELD_WARN], p.side));
+  HIP_TRY(hipMemsetAsync(p.field[DMC_FIELD_STATS], 0, b->bytes[DMC_FIELD_STATS], p.side));
+  DmcArgs init = a;               // dmc_batch_init_episode(seed, 0)
+  init.seed = p.seed;
+  if (launch_on(b, p.side, b->model->k_init, init, TASK_SETUP)) return -1;
+  DmcArgs settle = a;             // dmc_batch_step(NULL, ..., nsub, step_flags)
+  settle.nsub = p.nsub;
+  settle.nsteps = 1;
+  settle.flags |= DMC_FLAG_NO_OUTPUT |
+                  ((p.step_flags & DMC_STEP_STALE_FIRST) ? DMC_FLAG_STALE_FIRST : 0) |
+                  ((p.step_flags & DMC_STEP_ZERO_TIME) ? DMC_FLAG_ZERO_TIME : 0);
+  if (launch_on(b, p.side, b->model->k_step, settle, MODEL_SHAPED)) return -1;
+  HIP_TRY(hipEventRecord(p.done, p.side));
+  p.state = p.ISSUED;
+  return 0;
+}
+
+// `nsteps` more control steps have been issued on the batch's stream
+int prefetch_count(dmc_batch* b, int nsteps) {
+  dmc_batch::Prefetch& p = b->prefetch;
+  if (p.state != p.PENDING) return 0;
+  p.issued += nsteps;
+  if (p.issued < p.after_steps) return 0;
+  if (prefetch_issue(b)) {
+    p.state = p.NONE;    // (not tried again with every step)
+    return -1;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -228,7 +364,8 @@ extern "C" {
 // 101: dmc_model_info.nmodelparam, DMC_FIELD_MODELPARAM; 102: dmc_model_info.seq_launch;
 // 103: per-env episodes (dmc_batch_episodes_enable and what follows it in the header)
 // 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout)
-int dmc_version(void) { return 104; }
+// 105: episode prefetch (dmc_batch_episode_prefetch, dmc_batch_episode_take)
+int dmc_version(void) { return 105; }
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -497,10 +634,11 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
   // workspace: ws_per_env reals per env, laid out for the batch rounded up to
   // whole 64-env workgroups (surplus lanes of the last workgroup own a slot)
   const size_t npad = (n + 63)/64*64;
+  b->ws_bytes = atleast1(i.ws_per_env)*npad*rs;
   if (err == hipSuccess)
-    err = hipMalloc(&b->ws, atleast1(i.ws_per_env)*npad*rs);
+    err = hipMalloc(&b->ws, b->ws_bytes);
   if (err == hipSuccess)
-    err = hipMemsetAsync(b->ws, 0, atleast1(i.ws_per_env)*npad*rs, b->stream);
+    err = hipMemsetAsync(b->ws, 0, b->ws_bytes, b->stream);
   if (err == hipSuccess) err = hipEventCreate(&b->ev0);
   if (err == hipSuccess) err = hipEventCreate(&b->ev1);
   if (err != hipSuccess) {
@@ -520,6 +658,8 @@ int dmc_batch_create(const dmc_model* model, int nenv, dmc_batch** out) {
 
 void dmc_batch_free(dmc_batch* b) {
   if (!b) return;
+  // (not a word about b->model: a caller may have freed the model first)
+  prefetch_free(b);     // waits for the side stream: it reads the fields freed below
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (int f = 0; f < DMC_FIELD_COUNT; f++)
     if (b->field[f]) (void)hipFree(b->field[f]);
@@ -537,6 +677,7 @@ int dmc_batch_nenv(const dmc_batch* b) { return b ? b->nenv : 0; }
 
 int dmc_batch_set_aux_outputs(dmc_batch* b, int enabled) {
   if (!b) return fail("null batch");
+  if (b->aux_outputs != (enabled != 0) && prefetch_drop(b)) return -1;   // (the settle stores qacc or not)
   b->aux_outputs = enabled != 0;
   return 0;
 }
@@ -544,6 +685,7 @@ int dmc_batch_set_aux_outputs(dmc_batch* b, int enabled) {
 int dmc_batch_set_task_params(dmc_batch* b, int iparam, const double* r, int nr) {
   if (!b) return fail("null batch");
   if (nr < 0 || nr > 4) return fail("at most 4 real task parameters");
+  if (prefetch_drop(b)) return -1;
   b->task_param_i = iparam;
   for (int k = 0; k < nr; k++) b->task_param_r[k] = r[k];
   return 0;
@@ -600,6 +742,8 @@ int dmc_batch_write(dmc_batch* b, int field, const void* src, size_t bytes) {
     return fail("dmc_batch_write: field %d has %zu bytes, caller passed %zu",
                 field, b->bytes[field], bytes);
   HIP_TRY(hipSetDevice(b->model->device));
+  if ((field == DMC_FIELD_TASKDATA || field == DMC_FIELD_MODELPARAM) && prefetch_drop(b))
+    return -1;     // (a prefetch reads both)
   std::vector<char> tmp;
   if (flipped(b, field)) {
     tmp.resize(bytes);
@@ -682,7 +826,7 @@ int step_launch(dmc_batch* b, const void* ctrl, long long stride_k,
   a.ctrl_st = stride_t;
   if (launch(b, b->model->k_step, a, MODEL_SHAPED)) return -1;
   if (b->timing) b->launches += nsteps;   // (the timer's average stays per control step)
-  return 0;
+  return prefetch_count(b, nsteps);
 }
 
 }  // namespace
@@ -784,6 +928,7 @@ int dmc_batch_rollout(dmc_batch* b, const dmc_rollout* r) {
     a.action_out_st = r->action_stride_t;
     if (launch(b, b->model->k_step, a, MODEL_SHAPED)) return -1;
     if (b->timing) b->launches += chunk;   // (the timer's average stays per control step)
+    if (prefetch_count(b, chunk)) return -1;
     t += chunk;
   }
   return 0;
@@ -834,6 +979,7 @@ int dmc_batch_copy_state(dmc_batch* dst, const dmc_batch* src) {
       dst->model->info.nmodelparam != src->model->info.nmodelparam)
     return fail("dmc_batch_copy_state: incompatible batches");
   HIP_TRY(hipSetDevice(dst->model->device));
+  if (prefetch_drop(dst)) return -1;    // (task data and model parameters change)
   HIP_TRY(hipStreamSynchronize(src->stream));
   for (int f = 0; f < DMC_FIELD_COUNT; f++)
     HIP_TRY(hipMemcpyAsync(dst->field[f], src->field[f], dst->bytes[f],
@@ -856,6 +1002,7 @@ int dmc_batch_copy_state(dmc_batch* dst, const dmc_batch* src) {
 int dmc_batch_episodes_enable(dmc_batch* b, int step_limit) {
   if (!b) return fail("null batch");
   if (episode_block(b, "dmc_batch_episodes_enable")) return -1;
+  if (prefetch_drop(b)) return -1;      // (a whole-batch episode start no longer applies)
   b->episodes = true;
   b->step_limit = step_limit;
   return 0;
@@ -897,8 +1044,51 @@ int dmc_batch_mask_from_done(dmc_batch* b) {
 int dmc_batch_set_masked(dmc_batch* b, int on) {
   if (!b) return fail("null batch");
   if (on && episode_block(b, "dmc_batch_set_masked")) return -1;
+  if (on && prefetch_drop(b)) return -1;
   b->masked = on != 0;
   return 0;
+}
+
+int dmc_batch_episode_prefetch(dmc_batch* b, uint64_t seed, int settle_nsub, int step_flags,
+                               long long after_steps) {
+  if (!b) return fail("null batch");
+  if (b->masked || b->episodes)
+    return fail("dmc_batch_episode_prefetch: a prefetch is the start of a whole-batch "
+                "episode; the batch has %s",
+                b->episodes ? "per-env episodes enabled" : "an env mask set");
+  if (settle_nsub < 0) return fail("dmc_batch_episode_prefetch: settle_nsub must be >= 0");
+  if (after_steps < 0) return fail("dmc_batch_episode_prefetch: after_steps must be >= 0");
+  if (step_flags & ~(DMC_STEP_STALE_FIRST | DMC_STEP_ZERO_TIME))
+    return fail("dmc_batch_episode_prefetch: the settle steps take DMC_STEP_STALE_FIRST and "
+                "DMC_STEP_ZERO_TIME, no outputs (step_flags %d)", step_flags);
+  if ((step_flags & DMC_STEP_ZERO_TIME) && !(b->model->episode_caps & DMC_FLAG_ZERO_TIME))
+    return fail("dmc_batch_episode_prefetch: this code object does not take DMC_STEP_ZERO_TIME "
+                "(a team-mode build, or one built before version 103)");
+  dmc_batch::Prefetch& p = b->prefetch;
+  p.state = p.PENDING;      // (an earlier one is replaced; the side stream orders the two)
+  p.seed = seed;
+  p.nsub = settle_nsub;
+  p.step_flags = step_flags;
+  p.after_steps = after_steps;
+  p.issued = 0;
+  return prefetch_count(b, 0);
+}
+
+int dmc_batch_episode_take(dmc_batch* b, uint64_t seed, int settle_nsub, int step_flags) {
+  if (!b) return fail("null batch");
+  dmc_batch::Prefetch& p = b->prefetch;
+  const bool usable = p.state == p.ISSUED && p.seed == seed && p.nsub == settle_nsub &&
+                      p.step_flags == step_flags;
+  p.state = p.NONE;         // taken, or stale from here on
+  if (!usable) return 0;
+  HIP_TRY(hipSetDevice(b->model->device));
+  HIP_TRY(hipStreamWaitEvent(b->stream, p.done, 0));
+  for (dmc_field f : SHADOWED)
+    if (f != DMC_FIELD_QACC || p.qacc)
+      HIP_TRY(hipMemcpyAsync(b->field[f], p.field[f], b->bytes[f], hipMemcpyDeviceToDevice,
+                             b->stream));
+  HIP_TRY(hipMemcpyAsync(b->ws, p.ws, b->ws_bytes, hipMemcpyDeviceToDevice, b->stream));
+  return 1;
 }
 
 int dmc_batch_sync(dmc_batch* b) {
@@ -912,6 +1102,7 @@ int dmc_batch_set_stream(dmc_batch* b, void* stream, int external) {
   if (!b) return fail("null batch");
   HIP_TRY(hipSetDevice(b->model->device));
   HIP_TRY(hipStreamSynchronize(b->stream));
+  if (prefetch_drop(b)) return -1;
   b->stream = external ? (hipStream_t)stream : b->own_stream;
   return 0;
 }

@@ -591,6 +591,17 @@ class Physics(_control.Physics):
     if check:
       self.check_invalid_state()
 
+  def take_prefetched_episode(self, seed, n_sub_steps, stale_first=False, zero_time=False):
+    """True: the batch now holds what `batch.init_episode(seed)` and
+    `step(n_sub_steps, outputs=False, check=False, ...)` leave after `reset()`, from
+    the prefetch `batch.episode_prefetch` started with the same arguments.  False:
+    there was none to use and nothing changed; the caller runs the two."""
+    if not self._batch.episode_take(seed, n_sub_steps, stale_first, zero_time):
+      return False
+    self._pending_ctrl = None
+    self._dirty = True
+    return True
+
   def rollout_device(self, nsteps, n_sub_steps=1, ctrl=None, policy=None, obs_out=None,
                      reward_out=None, action_out=None):
     """`nsteps` control steps of `n_sub_steps` substeps in one launch per chunk

@@ -26,6 +26,7 @@ class Task(control.Task):
     self._device_init = bool(device_init)
     self._episode = 0
     self._streams = None
+    self._reset_at = None     # control steps the batch had issued at the last reset
 
   @property
   def random(self):
@@ -50,6 +51,22 @@ class Task(control.Task):
     self._episode += 1
     base = int(self._random.randint(0, 2**31 - 1))
     return (base << 20) + self._episode
+
+  def next_device_seed(self):
+    """What the next `device_seed()` returns if nobody draws from `self.random`
+    before it: drawn from a copy of the stream, which is left as it is."""
+    fork = np.random.RandomState()
+    fork.set_state(self._random.get_state())
+    return (int(fork.randint(0, 2**31 - 1)) << 20) + self._episode + 1
+
+  def prefetch_after_steps(self, control_steps):
+    """`after_steps` of the prefetch started at a reset: half the control steps
+    issued between the last two resets, so that the prefetch is neither still
+    running when the caller synchronises right after a reset nor late for the next
+    one; 0 (at once) before there are two.  control_steps: the batch's count of
+    issued control steps at this reset."""
+    last, self._reset_at = self._reset_at, int(control_steps)
+    return 0 if last is None else max(0, self._reset_at - last)//2
 
   def reset_done(self, physics, envs=None):
     """Starts a new episode in the envs that are done, and only there.

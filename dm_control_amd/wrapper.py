@@ -122,6 +122,8 @@ SIGNATURES = {
     'dmc_batch_episode_write': (_ci, [_vp, _ci, _vp, _cs]),
     'dmc_batch_mask_from_done': (_ci, [_vp]),
     'dmc_batch_set_masked': (_ci, [_vp, _ci]),
+    'dmc_batch_episode_prefetch': (_ci, [_vp, ctypes.c_uint64, _ci, _ci, _cll]),
+    'dmc_batch_episode_take': (_ci, [_vp, ctypes.c_uint64, _ci, _ci]),
     'dmc_batch_sync': (_ci, [_vp]),
     'dmc_batch_stream': (_vp, [_vp]),
     'dmc_batch_set_stream': (_ci, [_vp, _vp, _ci]),
@@ -250,6 +252,7 @@ class HipBatch:
     self.is_masked = False      # inside `masked()`
     self.episodes = False       # after `episodes_enable`
     self.step_limit = 0
+    self.control_steps = 0      # output-producing steps issued so far (settle steps: not counted)
     _check(self._lib.dmc_batch_create(model.ptr, self.nenv,
                                       ctypes.byref(self.ptr)))
 
@@ -331,6 +334,7 @@ class HipBatch:
     want_outputs = ((STEP_OUTPUTS if want_outputs else 0) |
                     (STEP_STALE_FIRST if stale_first else 0) |
                     (STEP_ZERO_TIME if zero_time else 0))
+    self.control_steps += want_outputs & STEP_OUTPUTS
     if ctrl is None:
       _check(self._lib.dmc_batch_step(self.ptr, None, 0, 0, 0, nsub,
                                       want_outputs))
@@ -348,12 +352,14 @@ class HipBatch:
     """ctrl_ptr: device address; element (k, env) at k*stride_k+env*stride_env."""
     _check(self._lib.dmc_batch_step(self.ptr, ctrl_ptr, stride_k, stride_env,
                                     1, nsub, int(want_outputs)))
+    self.control_steps += int(want_outputs) & STEP_OUTPUTS
 
   def step_device_n(self, ctrl_ptr, stride_k, stride_env, stride_t, nsteps,
                     nsub=1, want_outputs=True):
     """`nsteps` control steps; step t reads ctrl_ptr + t*stride_t reals."""
     _check(self._lib.dmc_batch_step_n(self.ptr, ctrl_ptr, stride_k, stride_env,
                                       stride_t, nsteps, nsub, int(want_outputs)))
+    self.control_steps += int(nsteps)*(int(want_outputs) & STEP_OUTPUTS)
 
   def rollout(self, nsteps, nsub=1, ctrl=None, policy=None, reward_out=None,
               obs_out=None, action_out=None):
@@ -378,6 +384,7 @@ class HipBatch:
         setattr(r, name + '_out', out[0])
         setattr(r, name + '_stride_t', out[1])
     _check(self._lib.dmc_batch_rollout(self.ptr, ctypes.byref(r)))
+    self.control_steps += r.nsteps
 
   # -- per-env episodes --------------------------------------------------------
   def episodes_enable(self, step_limit=0):
@@ -422,6 +429,34 @@ class HipBatch:
       yield self
     finally:
       self.set_masked(False)
+
+  # -- episode prefetch ----------------------------------------------------------
+  @staticmethod
+  def _settle_flags(stale_first, zero_time):
+    return ((STEP_STALE_FIRST if stale_first else 0) |
+            (STEP_ZERO_TIME if zero_time else 0))
+
+  def episode_prefetch(self, seed, settle_nsub, stale_first=False, zero_time=False,
+                       after_steps=0):
+    """Asks for the start of the next whole-batch episode -- reset,
+    `init_episode(seed)`, `settle_nsub` settle substeps -- to be computed on a side
+    stream into shadow buffers once `after_steps` more control steps have been
+    issued (`dmc_batch_episode_prefetch`).  Raises `Error` on a masked batch or
+    one with per-env episodes."""
+    _check(self._lib.dmc_batch_episode_prefetch(
+        self.ptr, int(seed) & (2**64 - 1), int(settle_nsub),
+        self._settle_flags(stale_first, zero_time), int(after_steps)))
+
+  def episode_take(self, seed, settle_nsub, stale_first=False, zero_time=False):
+    """True: the fields now hold (on the batch's stream, no host wait) what
+    `reset()`, `init_episode(seed)` and the settle step would have left, from a
+    prefetch with exactly these arguments.  False: there was none to use; run them."""
+    rc = self._lib.dmc_batch_episode_take(
+        self.ptr, int(seed) & (2**64 - 1), int(settle_nsub),
+        self._settle_flags(stale_first, zero_time))
+    if rc < 0:
+      _check(rc)
+    return rc == 1
 
   def clear_warnings(self):
     _check(self._lib.dmc_batch_clear_warnings(self.ptr))

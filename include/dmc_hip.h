@@ -104,7 +104,9 @@ typedef struct dmc_model_info {
  * 103: per-env episodes (dmc_batch_episodes_enable ... dmc_batch_set_masked, DMC_STEP_ZERO_TIME);
  *      code objects export `dmc_episode_caps`; older ones still load and step
  * 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout); rollout builds export
- *      `dmc_rollout_caps`, every other code object loads and steps as before */
+ *      `dmc_rollout_caps`, every other code object loads and steps as before
+ * 105: episode prefetch (dmc_batch_episode_prefetch, dmc_batch_episode_take); host side
+ *      only, every code object takes it */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
@@ -257,6 +259,46 @@ int dmc_batch_episode_read(dmc_batch* batch, int which, int* dst, size_t bytes);
 int dmc_batch_episode_write(dmc_batch* batch, int which, const int* src, size_t bytes);
 int dmc_batch_mask_from_done(dmc_batch* batch);
 int dmc_batch_set_masked(dmc_batch* batch, int on);
+
+/* Episode prefetch (version 105): the start of the batch's NEXT episode, computed beside
+ * the steps of the current one.  What a whole-batch reset launches on the batch's stream --
+ * dmc_batch_reset, dmc_batch_init_episode(seed, 0), then the settle steps of the task
+ * (dmc_batch_step without controls or outputs: `settle_nsub` substeps under `step_flags`,
+ * the DMC_STEP_* bits without DMC_STEP_OUTPUTS) -- depends on the seed, the model and the
+ * task data alone, not on anything the current episode computes.  A prefetch runs those
+ * launches on a side stream of the lowest priority into shadow copies of every field they
+ * write (state, warm start, time, data.ctrl, task data, warning mask, stats, episode
+ * return, and DMC_FIELD_QACC with the auxiliary outputs on) and of the workspace; the
+ * model parameters and task parameters are read from the batch.  With fewer workgroups
+ * than compute units (one env per lane: up to 64 envs per CU) it occupies units the step
+ * launches leave empty.
+ *
+ * dmc_batch_episode_prefetch records the request; it is issued from inside the
+ * dmc_batch_step / _step_n / _rollout call that brings the control steps issued since
+ * the request to `after_steps` (0: at once), ordered behind what the batch's stream holds
+ * at that moment.  (A prefetch issued right after a reset would still be running at the
+ * caller's next device-wide synchronisation, and be paid for there.)  A new request
+ * replaces an earlier one.  Refused with a message while an env mask is set or per-env
+ * episodes are enabled, and for step_flags with DMC_STEP_OUTPUTS.
+ *
+ * dmc_batch_episode_take returns 1 after making the batch's stream wait for a prefetch
+ * issued with exactly these arguments (an event; the host does not wait) and copying the
+ * shadows over the fields, device to device, on the batch's stream: the fields then hold,
+ * bit for bit, what dmc_batch_init_episode(seed, 0) and the settle step leave after a
+ * dmc_batch_reset.  Pointers handed out by dmc_batch_device_ptr stay valid.  It returns 0,
+ * and forgets the request, when there is nothing usable (none issued yet, other arguments,
+ * or dropped): the caller then runs the ordinary launches.  -1 is an error.
+ *
+ * A request is dropped (after waiting for the side stream) by whatever changes the
+ * prefetch's inputs or the launches of a reset: dmc_batch_write of task data or model
+ * parameters, dmc_batch_copy_state into the batch, dmc_batch_set_task_params,
+ * dmc_batch_set_aux_outputs, dmc_batch_set_masked(on), dmc_batch_episodes_enable and
+ * dmc_batch_set_stream.  A write to task data through dmc_batch_device_ptr is not seen:
+ * follow it with a new request.  A step call that issues the prefetch records an event
+ * and launches on a second stream: not inside a stream capture. */
+int dmc_batch_episode_prefetch(dmc_batch* batch, uint64_t seed, int settle_nsub,
+                               int step_flags, long long after_steps);
+int dmc_batch_episode_take(dmc_batch* batch, uint64_t seed, int settle_nsub, int step_flags);
 
 /* Rollouts (version 104): T control steps in one launch per chunk of at most
  * DMC_SEQ_LAUNCH_MAX_STEPS, with every step's reward, observation and control
