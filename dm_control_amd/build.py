@@ -64,6 +64,7 @@ def build_library(force=False):
   """Compiles the C-ABI runtime (include/dmc_hip.h) into libdmc_hip.so."""
   srcs = [os.path.join(_CSRC, 'dmc_api.cpp'),
           os.path.join(_CSRC, 'dmc_args.h'),
+          os.path.join(_CSRC, 'dmc_launch.h'),
           os.path.join(_CSRC, '..', '..', 'include', 'dmc_hip.h')]
   if not force and _newer(LIB_PATH, srcs):
     return LIB_PATH
