@@ -231,11 +231,16 @@ Spec = collections.namedtuple(
 
 
 def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
-         per_env=(), rollout=False):
+         per_env=(), rollout=False, population=False):
   """Checks the arguments of `build_model` and resolves them into a `Spec`.
   Pure: reads the environment, touches no file and starts no process.
   `per_env`: model fields the kernels read per env (codegen.PER_ENV_FIELDS).
-  `rollout`: the rollout variant of the one-env-per-lane kernel (-DDMC_ROLLOUT=1)."""
+  `rollout`: the rollout variant of the one-env-per-lane kernel (-DDMC_ROLLOUT=1).
+  `population`: the rollout variant whose policy evaluator reads its weights per
+  lane, one policy per group of envs (-DDMC_POLICY_POPULATION=1)."""
+  if population and not rollout:
+    raise ValueError('population=True is a variant of the rollout build: it needs '
+                     'rollout=True')
   if rollout and mode in ('coop', 'team'):
     raise ValueError('rollout=True is built for the one-env-per-lane kernel '
                      '(mode auto, unrolled or rolled), not for mode=%r' % mode)
@@ -286,6 +291,9 @@ def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
   if rollout:
     # per-step outputs and the device MLP policy (csrc/dmc_kernels.hip, DMC_ROLLOUT)
     flags += ('-DDMC_ROLLOUT=1',)
+  if population:
+    # one policy per group of envs (csrc/dmc_kernels.hip, DMC_POLICY_POPULATION)
+    flags += ('-DDMC_POLICY_POPULATION=1',)
   return Spec(model, task, ncon_max, precision, mode, group, lds_budget, source,
               'f64' if precision == 'f64' else 'f32', flags, tiers, per_env)
 
@@ -469,7 +477,8 @@ def realise(spec_, force=False, keep_temps=False):
 
 def build_model(model, task=codegen.TASK_NONE, precision='f32',
                 ncon_max=None, force=False, keep_temps=False, extra_flags=None,
-                mode='auto', lds_budget=None, group=64, per_env=(), rollout=False):
+                mode='auto', lds_budget=None, group=64, per_env=(), rollout=False,
+                population=False):
   """Generates the constants header for `model` and compiles its kernels.
 
   mode: "unrolled" (static indexing, per-lane state in registers), "rolled"
@@ -491,6 +500,10 @@ def build_model(model, task=codegen.TASK_NONE, precision='f32',
   rollout: True builds the rollout variant of the one-env-per-lane kernel
   (`dmc_batch_rollout`: per-step outputs, device MLP policy); it walks the same
   tiers and is refused (ValueError) for "coop" and "team".
+
+  population: True (with rollout=True, else a ValueError) builds the rollout
+  variant that takes a population of policies (`dmc_batch_rollout_population`:
+  env e acts with the weights of member e // (nenv // P)); the same tiers.
   """
   return realise(spec(model, task, precision, ncon_max, extra_flags, mode,
-                      lds_budget, group, per_env, rollout), force, keep_temps)
+                      lds_budget, group, per_env, rollout, population), force, keep_temps)

@@ -422,7 +422,8 @@ extern "C" {
 // 103: per-env episodes (dmc_batch_episodes_enable and what follows it in the header)
 // 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout)
 // 105: episode prefetch (dmc_batch_episode_prefetch, dmc_batch_episode_take)
-int dmc_version(void) { return 105; }
+// 106: populations of policies (dmc_batch_rollout_population)
+int dmc_version(void) { return 106; }
 
 const char* dmc_last_error(void) { return g_error.c_str(); }
 
@@ -723,6 +724,10 @@ int dmc_batch_step_n(dmc_batch* b, const void* ctrl, long long stride_k,
 int dmc_model_rollout_caps(const dmc_model* model) { return model ? model->rollout_caps : 0; }
 
 int dmc_batch_rollout(dmc_batch* b, const dmc_rollout* r) {
+  return dmc_batch_rollout_population(b, r, 1);
+}
+
+int dmc_batch_rollout_population(dmc_batch* b, const dmc_rollout* r, int members) {
   if (!b || !r) return fail("dmc_batch_rollout: null argument");
   const dmc_model_info& i = b->code.info;
   const int caps = b->code.rollout_caps;
@@ -734,6 +739,14 @@ int dmc_batch_rollout(dmc_batch* b, const dmc_rollout* r) {
                 b->episodes ? "per-env episodes enabled" : "an env mask set");
   if (r->nsteps < 0) return fail("dmc_batch_rollout: nsteps must be >= 0");
   if (r->nsub < 0) return fail("dmc_batch_rollout: nsub must be >= 0");
+  if (members < 1) return fail("dmc_batch_rollout_population: members must be >= 1, not %d", members);
+  if (members > 1 && !(caps & DMC_ROLLOUT_CAP_POPULATION))
+    return fail("dmc_batch_rollout_population: this code object takes one policy shared by the "
+                "batch; build the model with rollout=True, population=True "
+                "(-DDMC_POLICY_POPULATION=1)");
+  if (b->nenv % members != 0)
+    return fail("dmc_batch_rollout_population: %d members do not divide the %d envs of the batch "
+                "(env e acts with member e / (nenv/members))", members, b->nenv);
   if (r->policy) {
     const int cap = caps >> DMC_ROLLOUT_CAP_WIDTH_SHIFT;
     if (!(caps & DMC_ROLLOUT_CAP_POLICY))
@@ -752,7 +765,8 @@ int dmc_batch_rollout(dmc_batch* b, const dmc_rollout* r) {
   const int max = chunk_max(*b, true);
   for (int t = 0, chunk; t < r->nsteps; t += chunk) {
     chunk = next_chunk(t, r->nsteps, max);
-    if (launch(b, b->stream, b->model->k_step, rollout_args(*b, *b, *r, t, chunk), MODEL_SHAPED) ||
+    if (launch(b, b->stream, b->model->k_step, rollout_args(*b, *b, *r, t, chunk, members),
+               MODEL_SHAPED) ||
         steps_issued(b, chunk))
       return -1;
   }

@@ -49,9 +49,13 @@ struct DmcArgs {
   // ctrl[t] with DMC_FLAG_CTRL).  Weights shared by the batch, packed per layer as
   // W[out][in] row-major then b[out]: policy_nlayers (1 or 2) tanh layers of
   // policy_width[l] units, then the linear output layer of NU units.
+  // policy_members P > 1 (code objects with DMC_ROLLOUT_CAP_POPULATION): P policies of
+  // that shape, env e acting with member e / (nenv/P); word j of the packed order of
+  // member m at policy[j*P + m].  0 reads as 1, the shared block.
   DMC_CREALPTR policy;
   int policy_nlayers;
   int policy_width[2];
+  int policy_members;      // (where the pointer below left 4 bytes of padding)
   // per-step outputs of the launch's step t, each optional (null: not stored):
   DMC_REALPTR reward_out;  // [nenv] at reward_out + t*reward_out_st: reward of the state after step t
   DMC_REALPTR obs_out;     // [nenv][NOBS] at obs_out + t*obs_out_st: its observation
@@ -94,6 +98,7 @@ struct alignas(16) DmcInfo {
   int nmodelparam;        // rows of the model-parameter block
   int seq_launch;         // 1: dmc_step runs DmcArgs.nsteps control steps per launch
 };
+static_assert(sizeof(DmcArgs) == 352, "policy_members took padding: no member moved");
 static_assert(sizeof(DmcInfo) == 20*sizeof(int), "dmc_info is 20 ints");
 
 // `dmc_episode_caps`: a second device global next to `dmc_info` (whose size is
@@ -108,4 +113,5 @@ typedef int DmcEpisodeCaps;
 typedef int DmcRolloutCaps;
 #define DMC_ROLLOUT_CAP_OUTPUTS 1         // per-step reward / observation / action stores
 #define DMC_ROLLOUT_CAP_POLICY 2          // DMC_FLAG_POLICY
+#define DMC_ROLLOUT_CAP_POPULATION 4      // DmcArgs.policy_members > 1 (-DDMC_POLICY_POPULATION=1)
 #define DMC_ROLLOUT_CAP_WIDTH_SHIFT 8     // caps >> 8: the widest hidden layer it takes

@@ -4821,6 +4821,9 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
   if (accumulate) a.episode_return[e] += rew;
 }
 
+#if defined(DMC_POLICY_POPULATION) && !defined(DMC_ROLLOUT)
+#error "-DDMC_POLICY_POPULATION=1 is a variant of the rollout build: it needs -DDMC_ROLLOUT=1"
+#endif
 #ifdef DMC_ROLLOUT
 // ---------------------------------------------------------------------------
 // Rollout builds (-DDMC_ROLLOUT=1, one env per lane): dmc_step additionally
@@ -4828,7 +4831,8 @@ DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
 // can take the controls from an MLP over the observation (DMC_FLAG_POLICY).  An
 // env lives in one lane and so does its observation: the MLP is this lane's own
 // FMAs over weights whose addresses depend on kernel arguments and loop counters
-// only (wave-uniform: scalar loads).  A build without the define has none of this.
+// only (wave-uniform: scalar loads; with -DDMC_POLICY_POPULATION=1 on top, one policy
+// per group of envs: per-lane vector loads).  A build without the define has none of this.
 // ---------------------------------------------------------------------------
 static_assert(!TEAMED, "DMC_ROLLOUT is built for the one-env-per-lane kernel, not for team mode");
 #ifndef DMC_POLICY_MAX_WIDTH
@@ -4841,6 +4845,9 @@ constexpr int ROLLOUT_LDS_WORDS =
     LDS_WORDS > LANES*DMC_POLICY_MAX_WIDTH ? LDS_WORDS : LANES*DMC_POLICY_MAX_WIDTH;
 constexpr bool ROLLOUT_OBS_STAGE_FITS = ROLLOUT_LDS_WORDS >= LANES*(NOBS > 0 ? NOBS : 1);
 constexpr DmcRolloutCaps ROLLOUT_CAPS = DMC_ROLLOUT_CAP_OUTPUTS | DMC_ROLLOUT_CAP_POLICY |
+#ifdef DMC_POLICY_POPULATION
+                                        DMC_ROLLOUT_CAP_POPULATION |
+#endif
                                         (DMC_POLICY_MAX_WIDTH << DMC_ROLLOUT_CAP_WIDTH_SHIFT);
 
 // act <- MLP(obs).  `col`: this lane's LDS column (word k at col[k*LANES]); the
@@ -4863,16 +4870,145 @@ typedef const real __attribute__((address_space(4))) policy_word;
 // layer is evaluated POLICY_UNITS units at a time, and a runtime fan-in in chunks of
 // POLICY_CHUNK inputs: the rows' loads are issued together and waited for once.  A
 // unit's sum still runs over its inputs in order.
+// The evaluator below is written over the weight access (W, a template parameter) and
+// exists once per build.  policy_row(w, j) is the row that starts at word j of the
+// weights `w` (j wave-uniform).  A group of words goes through a PolicyStage<U, C>:
+// fetch(u, c, row) asks for word c of the row of unit u (c < POLICY_CHUNK, a constant
+// once the loops are unrolled), policy_issued() stands between the fetches of a group
+// and the sums over them, value(u, c, row) is the word.
+#ifndef DMC_POLICY_POPULATION
 constexpr int POLICY_UNITS = 4, POLICY_CHUNK = 16;
+typedef policy_word* policy_weights;
+// (scalar loads: nothing to fetch ahead, the load of w[j + c] stands where the value
+// is used and the compiler moves it up)
+struct PolicyRow { policy_word* w; int j; };
+__device__ __forceinline__ PolicyRow policy_row(policy_word* w, int j) { return {w, j}; }
+template <int U, int C> struct PolicyStage {
+  __device__ __forceinline__ void fetch(int, int, const PolicyRow&) {}
+  __device__ __forceinline__ real value(int, int c, const PolicyRow& row) const {
+    return row.w[row.j + c];
+  }
+};
+#define POLICY_REGS_CHUNK(fan_in) (fan_in)
+__device__ __forceinline__ void policy_issued() {}
+#else
+// Population builds (-DDMC_POLICY_POPULATION=1): env e acts with the weights of member
+// m = e / (nenv/P) of P policies of one shape; word j of member m is policy[j*P + m]
+// ([nparams][P], P = 1: the flat block).  The words are per lane, so they come through
+// vector loads: global_load at the wave-uniform address policy + j*P (scalar
+// arithmetic, one SGPR pair) plus a 32-bit lane offset, the saddr form.  The lane
+// offsets are the member's column plus c columns further, POLICY_ROW_WORDS VGPRs set up
+// once per evaluation: no address arithmetic per weight in the vector unit, and a group
+// of loads shares the base of its row (a base per load needs 2 SGPRs each, and 60 of
+// them spilled the cheetah build out of its tier).  The row base goes through an empty
+// asm with a scalar-register constraint: left to itself the compiler folds the row
+// into the lane offsets and carries a 64-bit VGPR address per weight (v_mad_u64_u32
+// for each, 60 register pairs).  One member per lane is a coalesced
+// wave access, a member per 64 lanes or more a broadcast of one word.  The loads of a
+// group of POLICY_UNITS x POLICY_CHUNK weights are in flight together; vmcnt counts to
+// 63, hence 3 units at a time where the shared evaluator takes 4 (16 inputs at a time
+// leave a width of 64 without a tail).
+constexpr int POLICY_UNITS = 3, POLICY_CHUNK = 16;
+static_assert(POLICY_UNITS*POLICY_CHUNK <= 63, "the loads of a group fit the vmcnt counter");
+// the words of a row that one group can ask for, each with a lane offset of its own
+constexpr int POLICY_ROW_WORDS = 63/POLICY_UNITS;
+static_assert(POLICY_CHUNK <= POLICY_ROW_WORDS && POLICY_UNITS <= POLICY_ROW_WORDS,
+              "a lane offset per input of a chunk and per unit of a group");
+#ifdef DMC_HOST_SHIM
+typedef const real policy_member_word;
+#else
+typedef const real __attribute__((address_space(1))) policy_member_word;   // (global, not flat)
+#endif
+struct PolicyMember {
+  policy_member_word* p;          // policy + j*P, wave-uniform
+  long long P;                    // members: the words between j and j + 1
+  unsigned lane[POLICY_ROW_WORDS];  // bytes from word (j, member 0) to word (j + c, this env's member)
+  __device__ __forceinline__ PolicyMember operator+(int j) const {
+    PolicyMember w = *this;
+    w.p += j*P;
+    return w;
+  }
+};
+typedef PolicyMember policy_weights;
+typedef PolicyMember PolicyRow;
+__device__ __forceinline__ PolicyRow policy_row(const PolicyMember& w, int j) {
+  PolicyMember row = w + j;
+#ifndef DMC_HOST_SHIM
+  asm("" : "+s"(row.p));
+#endif
+  return row;
+}
+template <int U, int C> struct PolicyStage {
+  static_assert(C <= POLICY_ROW_WORDS, "fetch(u, c, row) has a lane offset for every c < C");
+  real v[U][C];
+  __device__ __forceinline__ void fetch(int u, int c, const PolicyRow& row) {
+    unsigned lane = row.lane[c];
+#ifndef DMC_HOST_SHIM
+    asm("" : "+v"(lane));      // (the zero extension stays next to the load: the saddr form)
+#endif
+    v[u][c] = *(policy_member_word*)((uintptr_t)row.p + lane);
+  }
+  __device__ __forceinline__ real value(int u, int c, const PolicyRow&) const { return v[u][c]; }
+};
+// (the whole fan-in of the first layer at once where that fits the counter)
+#define POLICY_REGS_CHUNK(fan_in) ((fan_in) <= POLICY_ROW_WORDS ? (fan_in) : POLICY_CHUNK)
+// between the loads of a group and the sums over them: no load moves past it, so the
+// group is issued whole and waited for once (left to its pressure heuristics the
+// scheduler put each load next to its multiply: one memory latency per weight)
+__device__ __forceinline__ void policy_issued() {
+#ifndef DMC_HOST_SHIM
+  asm volatile("" ::: "memory");
+#endif
+}
+// the member of env e, as the byte offset of its column (computed once, at the
+// kernel's entry: one VGPR across the steps)
+DEV unsigned policy_member_offset(const DmcArgs& a, int e) {
+  const int P = a.policy_members < 1 ? 1 : a.policy_members;
+  const int g = a.nenv/P < 1 ? 1 : a.nenv/P;
+  const int m = e/g < P ? e/g : P - 1;
+  return (unsigned)m*(unsigned)sizeof(real);
+}
+DEV PolicyMember policy_member(const DmcArgs& a, unsigned member) {
+  PolicyMember w;
+  w.p = (policy_member_word*)a.policy;
+  w.P = a.policy_members < 1 ? 1 : a.policy_members;
+  DMC_UNROLL
+  for (int c = 0; c < POLICY_ROW_WORDS; c++)
+    w.lane[c] = member + (unsigned)c*(unsigned)w.P*(unsigned)sizeof(real);
+  return w;
+}
+#endif
 
+// a single word, fetched and used on the spot
+__device__ __forceinline__ real policy_word_at(const PolicyRow& row, int c) {
+  PolicyStage<1, POLICY_CHUNK> v;
+  v.fetch(0, c, row);
+  return v.value(0, c, row);
+}
 // x: the inputs in registers (fan-in FIN, a compile-time constant)
 template <int FIN> struct PolicyRegs {
   const real* x;
-  template <int U> __device__ __forceinline__ void dots(policy_word* w, int, real* s) const {
+  // (the whole fan-in at once where the weights are scalar loads; POLICY_CHUNK inputs
+  // at a time where they are counted vector loads)
+  template <int U, class W> __device__ __forceinline__ void dots(W w, int, real* s) const {
     DMC_UNROLL
-    for (int u = 0; u < U; u++)
+    for (int k0 = 0; k0 < FIN; k0 += POLICY_REGS_CHUNK(FIN)) {
+      constexpr int C = POLICY_REGS_CHUNK(FIN) > 0 ? POLICY_REGS_CHUNK(FIN) : 1;
+      PolicyStage<U, C> v;
       DMC_UNROLL
-      for (int k = 0; k < FIN; k++) s[u] += w[u*FIN + k]*x[k];
+      for (int u = 0; u < U; u++) {
+        const PolicyRow row = policy_row(w, u*FIN + k0);
+        DMC_UNROLL
+        for (int c = 0; c < C && k0 + c < FIN; c++) v.fetch(u, c, row);
+      }
+      policy_issued();
+      DMC_UNROLL
+      for (int u = 0; u < U; u++) {
+        const PolicyRow row = policy_row(w, u*FIN + k0);
+        DMC_UNROLL
+        for (int c = 0; c < C && k0 + c < FIN; c++) s[u] += v.value(u, c, row)*x[k0 + c];
+      }
+    }
   }
   __device__ __forceinline__ int fan_in() const { return FIN; }
 };
@@ -4880,78 +5016,99 @@ template <int FIN> struct PolicyRegs {
 struct PolicyColumn {
   const real* col;
   int n;
-  template <int U> __device__ __forceinline__ void dots(policy_word* w, int, real* s) const {
+  template <int U, class W> __device__ __forceinline__ void dots(W w, int, real* s) const {
     int k = 0;
     for (; k + POLICY_CHUNK <= n; k += POLICY_CHUNK) {
       real x[POLICY_CHUNK];
+      PolicyStage<U, POLICY_CHUNK> v;
+      DMC_UNROLL
+      for (int u = 0; u < U; u++) {
+        const PolicyRow row = policy_row(w, u*n + k);
+        DMC_UNROLL
+        for (int c = 0; c < POLICY_CHUNK; c++) v.fetch(u, c, row);
+      }
+      policy_issued();
       DMC_UNROLL
       for (int c = 0; c < POLICY_CHUNK; c++) x[c] = col[(k + c)*LANES];
       DMC_UNROLL
-      for (int u = 0; u < U; u++)
+      for (int u = 0; u < U; u++) {
+        const PolicyRow row = policy_row(w, u*n + k);
         DMC_UNROLL
-        for (int c = 0; c < POLICY_CHUNK; c++) s[u] += w[u*n + k + c]*x[c];
+        for (int c = 0; c < POLICY_CHUNK; c++) s[u] += v.value(u, c, row)*x[c];
+      }
     }
     for (; k < n; k++) {
       const real x = col[k*LANES];
       DMC_UNROLL
-      for (int u = 0; u < U; u++) s[u] += w[u*n + k]*x;
+      for (int u = 0; u < U; u++) s[u] += policy_word_at(policy_row(w, u*n + k), 0)*x;
     }
   }
   __device__ __forceinline__ int fan_in() const { return n; }
 };
 // h_j = tanh(b[j] + W[j] . x) for the `width` units of a layer, emit(j, U, h) for
 // every group of U consecutive units (POLICY_UNITS of them, then one at a time)
-template <class In, class Emit>
-DEV void policy_layer(policy_word* w, policy_word* b, int width, const In& in, Emit&& emit) {
+// (W: how the weights are read, policy_weights of the build)
+template <class W, class In, class Emit>
+DEV void policy_layer(W w, W b, int width, const In& in, Emit&& emit) {
   const int n = in.fan_in();
   int j = 0;
   for (; j + POLICY_UNITS <= width; j += POLICY_UNITS) {
     real h[POLICY_UNITS];
+    const PolicyRow bias = policy_row(b, j);
     DMC_UNROLL
-    for (int u = 0; u < POLICY_UNITS; u++) h[u] = b[j + u];
+    for (int u = 0; u < POLICY_UNITS; u++) h[u] = policy_word_at(bias, u);
     in.template dots<POLICY_UNITS>(w + j*n, n, h);
     DMC_UNROLL
     for (int u = 0; u < POLICY_UNITS; u++) h[u] = tanh(h[u]);
     emit(j, POLICY_UNITS, h);
   }
   for (; j < width; j++) {
-    real h[1] = {b[j]};
+    real h[1] = {policy_word_at(policy_row(b, j), 0)};
     in.template dots<1>(w + j*n, n, h);
     h[0] = tanh(h[0]);
     emit(j, 1, h);
   }
 }
 
-DEV void policy_mlp(const DmcArgs& a, const real* obs, real* act, real* col) {
-  policy_word* p = (policy_word*)a.policy;
+template <class W>
+DEV void policy_mlp(W p, const DmcArgs& a, const real* obs, real* act, real* col) {
   const int w0 = a.policy_width[0];
-  policy_word* b0 = p + w0*NOBS;
+  const W b0 = p + w0*NOBS;
   const PolicyRegs<NOBS> first = {obs};
   // the output layer, streamed: act += W[:, j..j+U) h
-  policy_word* wo;
+  W wo;
   int no;
   const auto output = [&](int j, int U, const real* h) {
+    PolicyStage<(NU > 0 ? NU : 1), POLICY_UNITS> v;
+    DMC_UNROLL
+    for (int i = 0; i < NU; i++) {
+      const PolicyRow row = policy_row(wo, i*no + j);
+      DMC_UNROLL
+      for (int u = 0; u < POLICY_UNITS; u++)
+        if (u < U) v.fetch(i, u, row);
+    }
+    policy_issued();
     for (int u = 0; u < U; u++)
       DMC_UNROLL
-      for (int i = 0; i < NU; i++) act[i] += wo[i*no + j + u]*h[u];
+      for (int i = 0; i < NU; i++) act[i] += v.value(i, u, policy_row(wo, i*no + j))*h[u];
   };
   if (a.policy_nlayers == 1) {
     wo = b0 + w0; no = w0;
-    policy_word* bo = wo + NU*w0;
+    const W bo = wo + NU*w0;
     DMC_UNROLL
-    for (int i = 0; i < NU; i++) act[i] = bo[i];
+    for (int i = 0; i < NU; i++) act[i] = policy_word_at(policy_row(bo, i), 0);
     policy_layer(p, b0, w0, first, output);
   } else {
     const int n1 = a.policy_width[1];
-    policy_word* w1 = b0 + w0;
-    policy_word* b1 = w1 + n1*w0;
+    const W w1 = b0 + w0;
+    const W b1 = w1 + n1*w0;
     wo = b1 + n1; no = n1;
-    policy_word* bo = wo + NU*n1;
+    const W bo = wo + NU*n1;
     policy_layer(p, b0, w0, first, [&](int j, int U, const real* h) {
       for (int u = 0; u < U; u++) col[(j + u)*LANES] = h[u];
     });
     DMC_UNROLL
-    for (int i = 0; i < NU; i++) act[i] = bo[i];
+    for (int i = 0; i < NU; i++) act[i] = policy_word_at(policy_row(bo, i), 0);
     policy_layer(w1, b1, n1, PolicyColumn{col, w0}, output);
   }
 }
@@ -5011,6 +5168,7 @@ DEV void late_copy(DmcArgs& d) {
   DMC_LATE(env_mask); DMC_LATE(ep_step); DMC_LATE(ep_done); DMC_LATE(step_limit);
   DMC_LATE(policy); DMC_LATE(policy_nlayers);
   for (int k = 0; k < 2; k++) DMC_LATE(policy_width[k]);
+  DMC_LATE(policy_members);
   DMC_LATE(reward_out); DMC_LATE(obs_out); DMC_LATE(action_out);
   DMC_LATE(reward_out_st); DMC_LATE(obs_out_st); DMC_LATE(action_out_st);
 }
@@ -5020,13 +5178,18 @@ static_assert(sizeof(DmcArgs) == 352, "late_copy names every member of DmcArgs")
 
 // control of the launch's step t: pi(o_t) if there is a policy, plus ctrl[t] if given
 // (a NaN / inf sum: mj_fwdActuation's ctrl check, warn and zero the controls); with
-// neither, the held control
+// neither, the held control.  `member`: policy_member_offset of a population build.
 template <class EnvT>
-DEV void rollout_control(EnvT& E, const DmcArgs& a, int e, int t, const real* obs, real* col) {
+DEV void rollout_control(EnvT& E, const DmcArgs& a, int e, int t, const real* obs, real* col,
+                         unsigned member) {
   const bool policy = (a.flags & DMC_FLAG_POLICY) != 0;
   if (a.flags & (DMC_FLAG_POLICY | DMC_FLAG_CTRL)) {
     real act[NU > 0 ? NU : 1];
-    if (policy) policy_mlp(a, obs, act, col);
+#ifdef DMC_POLICY_POPULATION
+    if (policy) policy_mlp(policy_member(a, member), a, obs, act, col);
+#else
+    if (policy) policy_mlp((policy_word*)a.policy, a, obs, act, col);
+#endif
     if (a.flags & DMC_FLAG_CTRL) {
       const real* ctrl = a.ctrl + (long long)t*a.ctrl_st;
       DMC_UNROLL
@@ -5115,6 +5278,11 @@ dmc_step(DmcArgs a) {
     DMC_UNROLL
     for (int k = 0; k < NOBS; k++) robs[k] = a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se];
   }
+#ifdef DMC_POLICY_POPULATION
+  const unsigned member = policy_member_offset(a, e);
+#else
+  const unsigned member = 0;
+#endif
 #endif
 #ifdef DMC_STEP_PROFILE
   const long long tk_ = wall_clock64();
@@ -5123,7 +5291,7 @@ dmc_step(DmcArgs a) {
 #ifdef DMC_ROLLOUT
     {
       DMC_LATE_ARGS(at);
-      rollout_control(E, at, e, t, robs, lds_rows + threadIdx.x);
+      rollout_control(E, at, e, t, robs, lds_rows + threadIdx.x, member);
     }
 #else
     if (TEAMED) {

@@ -152,9 +152,10 @@ inline DmcArgs step_args(const DmcState& s, const DmcTarget& tg, int want_output
   return a;
 }
 
-// the launch of steps [t, t + nsteps) of a rollout, every pointer advanced to step t
+// the launch of steps [t, t + nsteps) of a rollout, every pointer advanced to step t;
+// `members` policies at r.policy (1: the block says nothing of members, as it always did)
 inline DmcArgs rollout_args(const DmcState& s, const DmcTarget& tg, const dmc_rollout& r, int t,
-                            int nsteps) {
+                            int nsteps, int members = 1) {
   const int nu = s.code.info.nu;
   DmcArgs a = base_args(s, tg);
   a.nsub = r.nsub;
@@ -172,6 +173,7 @@ inline DmcArgs rollout_args(const DmcState& s, const DmcTarget& tg, const dmc_ro
     a.policy_nlayers = r.nlayers;
     a.policy_width[0] = r.width[0];
     a.policy_width[1] = r.nlayers == 2 ? r.width[1] : 0;
+    a.policy_members = members > 1 ? members : 0;
   }
   a.reward_out = advanced(s, r.reward_out, t*r.reward_stride_t);
   a.reward_out_st = r.reward_stride_t;

@@ -410,12 +410,18 @@ class Physics(_control.Physics):
 
   def __init__(self, model, batch_size=None, device=0, precision='f32',
                task=None, ncon_max=None, build_mode=None, group=None, per_env=(),
-               rollout=False):
+               rollout=False, population=False):
     """rollout: build the rollout variant of the one-env-per-lane kernel
     (`rollout_device`, `VecEnv.rollout`): whatever the batch size, the
-    several-lanes kernel is not selected."""
+    several-lanes kernel is not selected.  population: with rollout=True, the
+    rollout build that takes one policy per group of envs (`rollout_device` with
+    policy=(ptr, widths, members))."""
     self.model = model
     self._rollout = bool(rollout)
+    self._population = bool(population)
+    if self._population and not self._rollout:
+      raise ValueError('population=True is a variant of the rollout build: it needs '
+                       'rollout=True')
     if self._rollout and (build_mode or self._BUILD_MODE) in ('coop', 'team'):
       raise ValueError(
           'rollout=True runs on the one-env-per-lane kernel; this model is built for '
@@ -450,7 +456,7 @@ class Physics(_control.Physics):
     path = build.build_model(
         model, self._task_id, precision, ncon_max, mode=self._build_mode,
         lds_budget=build.lds_budget_for(self._batch_size), group=self._group,
-        per_env=self._params.per_env, rollout=self._rollout)
+        per_env=self._params.per_env, rollout=self._rollout, population=self._population)
     self._code_object = path
     self._hip_model = wrapper.HipModel(path, device)
     self._batch = wrapper.HipBatch(self._hip_model, self._batch_size)
@@ -611,7 +617,10 @@ class Physics(_control.Physics):
 
     ctrl: None or (ptr, stride_k, stride_env, stride_t) in elements; policy: None
     or (ptr, widths): the packed weights (`rl.policy.MLPPolicy.packed`) and the
-    hidden widths followed by the output width; obs_out / reward_out /
+    hidden widths followed by the output width, or (ptr, widths, members) on a
+    `Physics(..., rollout=True, population=True)`: [nparams, members] weights
+    (`rl.policy.MLPPopulation.packed`), env e acting with member
+    e // (batch_size // members); obs_out / reward_out /
     action_out: None or (ptr, stride_t): [nsteps, B, nobs], [nsteps, B], [nsteps, B, nu]
     written per step.  The fields afterwards hold the last step's outputs."""
     if not self._rollout:
@@ -753,7 +762,7 @@ class Physics(_control.Physics):
                      None if self._squeeze else self._batch_size,
                      self._device, self._precision, self._task_id,
                      self._ncon_max, self._build_mode, self._group, self._params.per_env,
-                     self._rollout)
+                     self._rollout, self._population)
     new._batch.copy_state_from(self._batch)
     for name, v in self._params.values.items():
       new._params.values[name][...] = v

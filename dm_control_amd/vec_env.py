@@ -39,9 +39,11 @@ class VecEnv:
   def __init__(self, domain_name, task_name, num_envs, seed=None,
                device=0, precision='f32', torch_io=False, task_kwargs=None,
                environment_kwargs=None, per_env=(), per_env_episodes=False,
-               episode_offsets=None, rollout=False):
+               episode_offsets=None, rollout=False, population=False):
     """rollout: build the rollout variant of the step kernel, for `rollout()`
     (torch mode, lock-step episodes, one-env-per-lane domains).
+    population: with rollout=True, the rollout build that takes an
+    `rl.policy.MLPPopulation`: one policy per group of consecutive envs.
     per_env_episodes: every env ends and restarts its episodes on its own
     (needs device_init, the default of torch mode).  episode_offsets: None,
     'staggered' (env e starts e/B of the way into its first episode) or int [B]:
@@ -60,6 +62,13 @@ class VecEnv:
         raise ValueError('rollout=True is lock-step: not with per_env_episodes=True')
       env_kw['rollout'] = True
       self._policy_cache = {}
+    self._population = bool(population or env_kw.get('population'))
+    if self._population:
+      if not self._rollout:
+        raise ValueError('population=True is a variant of the rollout build: it needs '
+                         'rollout=True')
+      env_kw['population'] = True
+    self._member_of_env, self._members = None, 0
     env_kw.setdefault('device_init', bool(torch_io))
     task_kw = dict(task_kwargs or {})
     task_kw.setdefault('random', seed)
@@ -208,28 +217,59 @@ class VecEnv:
     return obs, rewards, dones, infos
 
   # -- rollouts -------------------------------------------------------------------
+  @property
+  def member_of_env(self):
+    """int64 [B] on the device: the member env e acted with in the last rollout over
+    a population (e // (B // P)); per-member fitness is then one
+    `index_add_(0, member_of_env, episode_return)`, or `view(P, -1).mean(1)`."""
+    if self._member_of_env is None:
+      raise ValueError('member_of_env is set by a rollout over a population')
+    return self._member_of_env
+
   def _policy_device(self, policy):
-    """(device pointer, widths) of `policy`: uploaded once per policy object and
-    again after its `update_`."""
+    """(device pointer, widths[, members]) of `policy`: uploaded once per policy
+    object and again after its `update_`; a `from_device` population is read in place."""
     import torch
+    from dm_control_amd.rl import policy as policy_lib
+    members = None
+    if isinstance(policy, policy_lib.MLPPopulation):
+      members = policy.num_members
+      if not self._population:
+        raise ValueError('a population of policies needs VecEnv(..., rollout=True, '
+                         'population=True)')
+      if self.num_envs % members:
+        raise ValueError('%d members do not divide the %d envs' % (members, self.num_envs))
+      if self._members != members:
+        self._members = members
+        self._member_of_env = torch.arange(
+            self.num_envs, device=self._obs_t.device)//(self.num_envs//members)
     if policy.obs_dim != self.observation_dim or policy.action_dim != self.action_dim:
       raise ValueError('the policy maps %d -> %d values, the env %d -> %d'
                        % (policy.obs_dim, policy.action_dim, self.observation_dim,
                           self.action_dim))
+    if members is not None and policy.device_tensor is not None:
+      flat = policy.device_tensor
+      if flat.dtype != self._obs_t.dtype or flat.device != self._obs_t.device:
+        raise ValueError('the population tensor must be %s on %s, the env\'s own'
+                         % (self._obs_t.dtype, self._obs_t.device))
+      return flat.data_ptr(), policy.widths, members
     held = self._policy_cache.get(id(policy))
     if held is None or held[0] is not policy or held[1] != policy.version:
       flat = torch.from_numpy(policy.packed(self._physics.dtype)).to(self._obs_t.device)
       held = (policy, policy.version, flat)
       self._policy_cache[id(policy)] = held
+    if members is not None:
+      return held[2].data_ptr(), policy.widths, members
     return held[2].data_ptr(), policy.widths
 
   def rollout(self, T, policy=None, actions=None, noise=None):
     """Up to `T` control steps in one kernel launch per 64 steps, no host round
     trip in between (`VecEnv(..., torch_io=True, rollout=True)`).
 
-    policy: an `rl.policy.MLPPolicy`, evaluated by the step kernel on each env's
-    observation: a_t = policy(o_t) + noise[t], `noise` an optional CUDA tensor
-    [T, B, nu].  Without a policy, `actions` [T, B, nu] is the action sequence
+    policy: an `rl.policy.MLPPolicy`, or on a `population=True` env an
+    `rl.policy.MLPPopulation` of P members (env e acts with member e // (B // P),
+    `member_of_env`), evaluated by the step kernel on each env's observation:
+    a_t = policy(o_t) + noise[t], `noise` an optional CUDA tensor [T, B, nu].  Without a policy, `actions` [T, B, nu] is the action sequence
     (open loop).  Runs n = min(T, steps left in the episode) steps and returns a
     dict of CUDA tensors: obs [n, B, D] (obs[t]: the observation after step t),
     actions [n, B, nu], rewards [n, B], dones [n, B] (the last row true when the

@@ -69,7 +69,7 @@ _vp, _ci, _cll, _cs = (ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong,
                        ctypes.c_size_t)
 
 # enum dmc_rollout_cap
-ROLLOUT_OUTPUTS, ROLLOUT_POLICY, ROLLOUT_WIDTH_SHIFT = 1, 2, 8
+ROLLOUT_OUTPUTS, ROLLOUT_POLICY, ROLLOUT_POPULATION, ROLLOUT_WIDTH_SHIFT = 1, 2, 4, 8
 
 
 class Rollout(ctypes.Structure):
@@ -111,6 +111,7 @@ SIGNATURES = {
     'dmc_batch_step_n': (_ci, [_vp, _vp, _cll, _cll, _cll, _ci, _ci, _ci]),
     'dmc_model_rollout_caps': (_ci, [_vp]),
     'dmc_batch_rollout': (_ci, [_vp, ctypes.POINTER(Rollout)]),
+    'dmc_batch_rollout_population': (_ci, [_vp, ctypes.POINTER(Rollout), _ci]),
     'dmc_batch_read': (_ci, [_vp, _ci, _vp, _cs]),
     'dmc_batch_field_bytes': (_cs, [_vp, _ci]),
     'dmc_batch_device_ptr': (_vp, [_vp, _ci]),
@@ -367,14 +368,20 @@ class HipBatch:
 
     ctrl: None or (ptr, stride_k, stride_env, stride_t), in reals; policy: None
     or (ptr, widths) with widths = hidden widths then the output width (nu), the
-    weights packed as `rl.policy.MLPPolicy.packed` lays them out; *_out: None or
-    (ptr, stride_t): [nsteps][nenv], [nsteps][nenv][nobs], [nsteps][nenv][nu]."""
+    weights packed as `rl.policy.MLPPolicy.packed` lays them out, or (ptr, widths,
+    members): `dmc_batch_rollout_population` over [nparams][members] weights as
+    `rl.policy.MLPPopulation.packed` lays them out, env e acting with member
+    e // (nenv // members); *_out: None or (ptr, stride_t): [nsteps][nenv],
+    [nsteps][nenv][nobs], [nsteps][nenv][nu]."""
     r = Rollout()
     r.nsteps, r.nsub = int(nsteps), int(nsub)
     if ctrl is not None:
       r.ctrl, r.ctrl_stride_k, r.ctrl_stride_env, r.ctrl_stride_t = ctrl
+    members = None
     if policy is not None:
-      ptr, widths = policy
+      ptr, widths = policy[:2]
+      if len(policy) > 2:
+        members = int(policy[2])
       widths = [int(w) for w in widths]
       r.policy, r.nlayers = ptr, len(widths) - 1
       for l, w in enumerate(widths[:3]):
@@ -383,7 +390,10 @@ class HipBatch:
       if out is not None:
         setattr(r, name + '_out', out[0])
         setattr(r, name + '_stride_t', out[1])
-    _check(self._lib.dmc_batch_rollout(self.ptr, ctypes.byref(r)))
+    if members is None:
+      _check(self._lib.dmc_batch_rollout(self.ptr, ctypes.byref(r)))
+    else:
+      _check(self._lib.dmc_batch_rollout_population(self.ptr, ctypes.byref(r), members))
     self.control_steps += r.nsteps
 
   # -- per-env episodes --------------------------------------------------------

@@ -106,7 +106,9 @@ typedef struct dmc_model_info {
  * 104: rollouts (dmc_model_rollout_caps, dmc_batch_rollout); rollout builds export
  *      `dmc_rollout_caps`, every other code object loads and steps as before
  * 105: episode prefetch (dmc_batch_episode_prefetch, dmc_batch_episode_take); host side
- *      only, every code object takes it */
+ *      only, every code object takes it
+ * 106: populations of policies (dmc_batch_rollout_population, DMC_ROLLOUT_POPULATION);
+ *      `dmc_rollout` is unchanged and every older code object rolls out as before */
 int dmc_version(void);
 const char* dmc_last_error(void);
 int dmc_device_count(void);
@@ -330,6 +332,7 @@ int dmc_batch_episode_take(dmc_batch* batch, uint64_t seed, int settle_nsub, int
 enum dmc_rollout_cap {
   DMC_ROLLOUT_OUTPUTS = 1,        /* per-step outputs */
   DMC_ROLLOUT_POLICY = 2,         /* device MLP policy */
+  DMC_ROLLOUT_POPULATION = 4,     /* one policy per group of envs (version 106) */
   DMC_ROLLOUT_WIDTH_SHIFT = 8     /* caps >> 8: the widest hidden layer */
 };
 typedef struct dmc_rollout {
@@ -348,6 +351,19 @@ typedef struct dmc_rollout {
 } dmc_rollout;
 int dmc_model_rollout_caps(const dmc_model* model);
 int dmc_batch_rollout(dmc_batch* batch, const dmc_rollout* rollout);
+/* Populations (version 106): the same rollout with `members` = P policies of one shape
+ * (evolution strategies, population-based training, sweeps, K checkpoints).  The nenv
+ * envs are split into P groups of nenv/P consecutive envs, and env e acts with member
+ * m = e / (nenv/P).  rollout->policy then holds [nparams][P] elements of the code
+ * object's real type, one column per member: word j of member m at policy[j*P + m],
+ * with j running over the packed order of a single policy (per layer W[out][in]
+ * row-major, then b[out]).  P = 1 is the flat block of dmc_batch_rollout, which is this
+ * call with members = 1.  Needs a code object whose capability word has
+ * DMC_ROLLOUT_POPULATION (build.build_model(..., rollout=True, population=True)) for
+ * members > 1; members < 1 and a member count that does not divide nenv are refused.
+ * A member whose weights make a control NaN / inf raises DMC_WARN_BADCTRL in its own
+ * envs only. */
+int dmc_batch_rollout_population(dmc_batch* batch, const dmc_rollout* rollout, int members);
 
 /* timing of the step kernel on the batch's own stream (HIP events around the
  * launches issued since dmc_batch_timer_start); returns accumulated device
