@@ -123,6 +123,8 @@ def model_key(model, task, precision, ncon_max=None, extra_flags=(),
       '' if unroll is True else ('semi' if unroll == 'semi' else ' '.join(_ROLLED_FLAGS)))).encode())
   if per_env:       # (nothing added for (): the key of a build without per-env fields)
     h.update(('/per_env=' + ','.join(per_env)).encode())
+  if task == codegen.TASK_SOCCER:   # the pitch is compiled in and is not a model field
+    h.update(('/soccer_pitch=%r' % (codegen.soccer_pitch_of(model),)).encode())
   for path in (src, os.path.join(_CSRC, 'dmc_coop.hip'),
                os.path.join(_CSRC, 'dmc_args.h'), codegen.__file__):
     with open(path, 'rb') as f:
@@ -253,6 +255,11 @@ def spec(model, task, precision, ncon_max, extra_flags, mode, lds_budget, group,
     raise ValueError('precision must be "f32", "f64" or "mixed"')
   if mode not in ('auto', 'unrolled', 'rolled', 'coop', 'team'):
     raise ValueError('mode must be auto, unrolled, rolled, coop or team')
+  if task == codegen.TASK_SOCCER and mode not in ('team', 'rolled'):
+    raise ValueError('TASK_SOCCER is an output stage of the team kernel (mode "team", or '
+                     '"rolled": the same source with one lane), not of mode=%r' % mode)
+  if task == codegen.TASK_SOCCER and (rollout or precision == 'mixed'):
+    raise ValueError('TASK_SOCCER has no rollout and no mixed-precision build')
   if precision == 'mixed' and mode in ('coop', 'team'):
     raise ValueError('precision "mixed" is built for the one-env-per-lane kernel')
   if extra_flags is None:

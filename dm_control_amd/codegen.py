@@ -24,6 +24,7 @@ from dm_control_amd.mjcf import model as mdl
 TASK_NONE, TASK_CARTPOLE, TASK_CHEETAH, TASK_HUMANOID = 0, 1, 2, 3
 TASK_WALKER, TASK_PENDULUM, TASK_ACROBOT, TASK_HOPPER = 4, 5, 6, 7
 TASK_REACHER, TASK_POINTMASS = 8, 9
+TASK_SOCCER = 10      # locomotion/soccer: per-player observables, goal code, off-court flag
 SENS_TOUCH = 0
 
 _SUPPORTED_PAIRS = {
@@ -193,7 +194,148 @@ def task_bodies(m, task):
   return [0]
 
 
+# ---------------------------------------------------------------------------
+# TASK_SOCCER: the task layer of locomotion/soccer as an output stage of the
+# team kernel.  One definition of the observation row for the header and Python.
+# ---------------------------------------------------------------------------
+CMU_WALKER_EXTENTS = (63, 62, 56)     # nq, nv, nu of one CMU humanoid tree
+# the eight arena features in the order a home player sees them (an away player
+# sees the list rotated by four) and their widths
+SOCCER_ARENA = (('team_goal_back_right', 2), ('team_goal_mid', 3),
+                ('team_goal_front_left', 2), ('field_front_left', 2),
+                ('opponent_goal_back_left', 2), ('opponent_goal_mid', 3),
+                ('opponent_goal_front_right', 2), ('field_back_right', 2))
+SOCCER_GAME_WORDS = 2                 # goal code, off-court flag
+
+
+def soccer_observation_layout(num_players, walker=CMU_WALKER_EXTENTS):
+  """Ordered {(player, name): (offset, extent)} of the TASK_SOCCER observation
+  row, closed by 'game': (offset, 2).  A player's block holds the keys of
+  `locomotion.soccer.Task.get_observation` in its order; players are the home
+  team then the away team, `walker` = (nq, nv, nu) of one player's tree.  The
+  one definition that the kernel (through the generated header) and the Python
+  side share."""
+  num_players = int(num_players)
+  if num_players < 2 or num_players % 2:
+    raise ValueError('two teams of equal size: num_players must be even and >= 2, got %d'
+                     % num_players)
+  nq, nv, nu = (int(v) for v in walker)
+  half = num_players//2
+  layout, offset = collections.OrderedDict(), 0
+  def put(key, extent):
+    nonlocal offset
+    layout[key] = (offset, extent)
+    offset += extent
+  for p in range(num_players):
+    put((p, 'joints_pos'), nq - 7)
+    put((p, 'joints_vel'), nv - 6)
+    put((p, 'body_height'), 1)
+    put((p, 'world_zaxis'), 3)
+    put((p, 'prev_action'), nu)
+    put((p, 'ball_ego_angular_velocity'), 3)
+    put((p, 'ball_ego_position'), 3)
+    put((p, 'ball_ego_linear_velocity'), 3)
+    mates = foes = 0
+    for j in range(num_players):
+      if j == p:
+        continue
+      if (j < half) == (p < half):
+        prefix, mates = 'teammate_%d' % mates, mates + 1
+      else:
+        prefix, foes = 'opponent_%d' % foes, foes + 1
+      put((p, prefix + '_ego_linear_velocity'), 3)
+      put((p, prefix + '_ego_position'), 3)
+      put((p, prefix + '_ego_orientation'), 9)
+    for name, dim in SOCCER_ARENA:
+      put((p, name), dim)
+  put('game', SOCCER_GAME_WORDS)
+  return layout
+
+
+def soccer_trees(m):
+  """(players, ball) of a soccer scene: players = [(qpos adr, dof adr, actuator
+  adr)] of the walker trees, (nq, nv, nu) of one of them, ball = (qpos adr, dof
+  adr).  The players are all kinematic trees but the last, each hanging from the
+  world by a free joint and all of equal extents; the ball is the last tree, a
+  single free body without actuators.  UnsupportedModelError otherwise."""
+  roots, tree = _trees_of(m)
+  if m.nbody < 2 or len(roots) < 3:
+    raise UnsupportedModelError('TASK_SOCCER needs two or more walker trees and a ball tree')
+  if m.nsensor:
+    raise UnsupportedModelError('TASK_SOCCER: scenes with sensors are not built')
+  width_q = {mdl.JNT_FREE: 7, mdl.JNT_BALL: 4}
+  width_v = {mdl.JNT_FREE: 6, mdl.JNT_BALL: 3}
+  found = []
+  for t in range(len(roots)):
+    jnts = [j for j in range(m.njnt) if tree[int(m.jnt_bodyid[j])] == t]
+    if not jnts or int(m.jnt_type[jnts[0]]) != mdl.JNT_FREE or \
+        int(m.jnt_bodyid[jnts[0]]) != roots[t]:
+      raise UnsupportedModelError('TASK_SOCCER: tree %d does not hang from a free joint' % t)
+    acts = []
+    for u in range(m.nu):
+      if int(m.actuator_trntype[u]) == mdl.TRN_TENDON:
+        raise UnsupportedModelError('TASK_SOCCER: tendon actuators are not built')
+      if int(m.actuator_trnid[u]) in jnts:
+        acts.append(u)
+    if acts and acts != list(range(acts[0], acts[0] + len(acts))):
+      raise UnsupportedModelError('TASK_SOCCER: the actuators of tree %d are not consecutive' % t)
+    found.append(dict(
+        qadr=int(m.jnt_qposadr[jnts[0]]), vadr=int(m.jnt_dofadr[jnts[0]]),
+        uadr=acts[0] if acts else 0, njnt=len(jnts),
+        nq=sum(width_q.get(int(m.jnt_type[j]), 1) for j in jnts),
+        nv=sum(width_v.get(int(m.jnt_type[j]), 1) for j in jnts), nu=len(acts)))
+  ball, walkers = found[-1], found[:-1]
+  if ball['njnt'] != 1 or ball['nu'] != 0:
+    raise UnsupportedModelError('TASK_SOCCER: the last tree is not a ball (one free body '
+                                'without actuators)')
+  if len(walkers) % 2:
+    raise UnsupportedModelError('TASK_SOCCER: two teams of equal size need an even number '
+                                'of walker trees, got %d' % len(walkers))
+  extents = (walkers[0]['nq'], walkers[0]['nv'], walkers[0]['nu'])
+  for t, wk in enumerate(walkers):
+    if (wk['nq'], wk['nv'], wk['nu']) != extents:
+      raise UnsupportedModelError(
+          'TASK_SOCCER: the players differ: tree %d has (nq, nv, nu) = %r, tree 0 %r'
+          % (t, (wk['nq'], wk['nv'], wk['nu']), extents))
+  return ([(wk['qadr'], wk['vadr'], wk['uadr']) for wk in walkers], extents,
+          (ball['qadr'], ball['vadr']))
+
+
+def soccer_pitch_of(m):
+  """The five numbers of pitch and goal geometry a TASK_SOCCER build compiles in:
+  (half length, half width, goal half depth, goal half width, goal half height),
+  the model's `soccer_pitch` attribute (set by `locomotion.soccer.load`)."""
+  pitch = getattr(m, 'soccer_pitch', None)
+  if pitch is None or len(pitch) != 5:
+    raise UnsupportedModelError(
+        'TASK_SOCCER needs model.soccer_pitch = (half length, half width, goal half '
+        'depth, goal half width, goal half height)')
+  return tuple(float(v) for v in pitch)
+
+
+def soccer_boxes(pitch):
+  """Detector boxes and arena features of the pitch, with the expressions of
+  `locomotion.soccer.PitchGeometry` (fp64): dict of home_lo, home_hi, away_lo,
+  away_hi [3], field_lo, field_hi [2] and features [8][3] in SOCCER_ARENA order
+  (2-vectors padded with 0)."""
+  lx, ly, gd, gw, gh = pitch
+  home = np.array([-lx + gd + 0.0, 0.0, gh])
+  away = np.array([lx - gd - 0.0, 0.0, gh])
+  half = np.array([gd, gw, gh])
+  fhalf = np.array([lx - 2*gd, ly - 2*gd])
+  box = dict(home_lo=home - half, home_hi=home + half, away_lo=away - half,
+             away_hi=away + half, field_lo=-fhalf, field_hi=fhalf)
+  feats = [box['home_lo'][:2], home, box['home_hi'][:2], box['field_hi'],
+           box['away_hi'][:2], away, box['away_lo'][:2], box['field_lo']]
+  box['features'] = np.array([list(f) + [0.0]*(3 - len(f)) for f in feats])
+  return box
+
+
 def observation_size(m, task):
+  if task == TASK_SOCCER:
+    players, extents, _ = soccer_trees(m)
+    return next(reversed(soccer_observation_layout(len(players), extents).values()))[0] \
+        + SOCCER_GAME_WORDS
   if task == TASK_CARTPOLE:
     return 1 + 2*(m.nbody - 2) + m.nv
   if task == TASK_CHEETAH:
@@ -468,6 +610,8 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=(), n
     w('#define DMC_MP_%s %d' % (name.upper(), offset))
   if layout:
     w('#define DMC_NMODELPARAM %d' % sum(n for _, n in layout.values()))
+  if task == TASK_SOCCER:
+    w('#define DMC_TASK_SOCCER 1')
   w('namespace dmc_model {')
 
   def ci(name, v):
@@ -545,6 +689,8 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=(), n
   tr('pair_friction', pair_fric); tr('pair_K', pair_k); tr('pair_B', pair_b)
   tr('pair_solimp', pair_solimp); tr('pair_diag', pair_diag)
   ti('task_body', (task_bodies(m, task) + [0]*6)[:6])
+  if task == TASK_SOCCER:
+    _soccer_constants(m, w, ci, ti)
   sites = task_sites(m, task)
   # touch sensors: the zone is the sensor's site, a sphere or a box
   # (mj_sensorAcc, mjSENS_TOUCH; wrapper/core_test.py:329-344 uses a box site)
@@ -793,6 +939,42 @@ def generate_header(m, task=TASK_NONE, ncon_max=None, unroll=None, per_env=(), n
   ti('pair_nrow', [1 if mx['dim'] == 1 else 2*(mx['dim'] - 1) for mx in mixed])
   w('}  // namespace dmc_model')
   return '\n'.join(out) + '\n'
+
+
+def _soccer_constants(m, w, ci, ti):
+  """The TASK_SOCCER block of the header: the players' and the ball's addresses
+  from the model's trees, the offsets of `soccer_observation_layout` inside a
+  player's block, and the pitch (fp64: the detector compares in double, so its
+  verdict is the host's for the same ball position in either precision)."""
+  players, extents, ball = soccer_trees(m)
+  layout = soccer_observation_layout(len(players), extents)
+  box = soccer_boxes(soccer_pitch_of(m))
+  w('// soccer pitch %r' % (soccer_pitch_of(m),))
+  ci('SOC_NP', len(players))
+  ci('SOC_NQW', extents[0]); ci('SOC_NVW', extents[1]); ci('SOC_NUW', extents[2])
+  ci('SOC_D', layout[(1, 'joints_pos')][0])
+  ci('SOC_BALL_Q', ball[0]); ci('SOC_BALL_V', ball[1])
+  ti('soc_qadr', [p[0] for p in players])
+  ti('soc_vadr', [p[1] for p in players])
+  ti('soc_uadr', [p[2] for p in players])
+  keys = [k for k in layout if k != 'game' and k[0] == 0]
+  first_other = next(k for k in keys if k[1].endswith('_ego_linear_velocity')
+                     and not k[1].startswith('ball'))
+  for name, key in (('JOINTS_POS', (0, 'joints_pos')), ('JOINTS_VEL', (0, 'joints_vel')),
+                    ('BODY_HEIGHT', (0, 'body_height')), ('WORLD_ZAXIS', (0, 'world_zaxis')),
+                    ('PREV_ACTION', (0, 'prev_action')),
+                    ('BALL', (0, 'ball_ego_angular_velocity')), ('OTHERS', first_other),
+                    ('ARENA', (0, SOCCER_ARENA[0][0]))):
+    ci('SOC_O_' + name, layout[key][0])
+  arena0 = layout[(0, SOCCER_ARENA[0][0])][0]
+  ti('soc_arena_off', [layout[(0, name)][0] - arena0 for name, _ in SOCCER_ARENA]
+     + [layout[(1, 'joints_pos')][0] - arena0])
+  ti('soc_arena_dim', [dim for _, dim in SOCCER_ARENA])
+  def td(name, vals):
+    w('static __device__ constexpr double %s[] = {%s};' % (name, _fmt(vals, 'real')))
+  td('soc_feature', box['features'])
+  for name in ('home_lo', 'home_hi', 'away_lo', 'away_hi', 'field_lo', 'field_hi'):
+    td('soc_' + name, box[name])
 
 
 def model_info(m, task=TASK_NONE, ncon_max=None, nefc_max=None):

@@ -351,7 +351,7 @@ enum { WARN_INERTIA = 1, WARN_CONTACTFULL = 2, WARN_CNSTRFULL = 4,
        WARN_BADCTRL = 128 };
 enum { TASK_NONE = 0, TASK_CARTPOLE = 1, TASK_CHEETAH = 2, TASK_HUMANOID = 3,
        TASK_WALKER = 4, TASK_PENDULUM = 5, TASK_ACROBOT = 6, TASK_HOPPER = 7,
-       TASK_REACHER = 8, TASK_POINTMASS = 9 };
+       TASK_REACHER = 8, TASK_POINTMASS = 9, TASK_SOCCER = 10 };
 
 #define DMC_REALPTR real*
 #define DMC_CREALPTR const real*
@@ -4636,6 +4636,8 @@ DEV real task_outputs(const EnvT& E, const DmcArgs& a, real* obs) {
     }
     reward = tolerance(sqrt(d2), 0, R(task_site_size[1]),
                        (a.task_param_i & 1) ? R(0) : R(1), SIG_GAUSSIAN, R(0.1));
+  } else if (TASK == TASK_SOCCER) {
+    // (store_outputs writes the row itself, a word per lane: soccer_outputs)
   } else {
     DMC_UNROLL
     for (int i = 0; i < NQ; i++) OBS(i) = E.qpos[i];
@@ -4796,9 +4798,128 @@ DEV void write_outputs(const Env& E, const DmcArgs& a, int e, const real* obs, r
   a.stats[e] = E.ncon; a.stats[n + e] = E.nefc + E.nmerged; a.stats[2*n + e] = E.iters;
 }
 
+#ifdef DMC_TASK_SOCCER
+// ---------------------------------------------------------------------------
+// TASK_SOCCER (locomotion/soccer, `fused_task=True`): the observables of every
+// player, the goal code and the off-court flag of the state in E, straight from
+// qpos / qvel -- a player's frame is its root quaternion, so nothing here needs
+// the kinematics.  The row is codegen.soccer_observation_layout: SOC_NP blocks of
+// SOC_D words, then the game block.  The lanes of a team share the words; a lane
+// computes a word from scratch (its player's rotation matrix included: 9 products
+// against a 4-byte store every TEAM words).
+// ---------------------------------------------------------------------------
+static_assert(DMC_GENERIC_BUILD, "TASK_SOCCER is built from the generic source (mode team / rolled)");
+static_assert(NSENSOR == 0 && NTOUCH == 0, "TASK_SOCCER: scenes without sensors");
+static_assert(NOBS == SOC_NP*SOC_D + 2, "the observation row: a block per player and the game block");
+#ifdef DMC_ROLLOUT
+#error "TASK_SOCCER has no rollout build"
+#endif
+// locomotion/soccer/__init__.py, _quat_to_mat
+DEV void soccer_mat(const real* q, real* m) {
+  const real w = q[0], x = q[1], y = q[2], z = q[3];
+  m[0] = 1 - 2*(y*y + z*z); m[1] = 2*(x*y - w*z); m[2] = 2*(x*z + w*y);
+  m[3] = 2*(x*y + w*z); m[4] = 1 - 2*(x*x + z*z); m[5] = 2*(y*z - w*x);
+  m[6] = 2*(x*z - w*y); m[7] = 2*(y*z + w*x); m[8] = 1 - 2*(x*x + y*y);
+}
+// word w of player p's block
+DEV real soccer_word(const Env& E, const DmcArgs& a, int e, int p, int w) {
+  const int qa = soc_qadr[p], va = soc_vadr[p];
+  if (w < SOC_O_JOINTS_VEL) return E.qpos[qa + 7 + w];
+  if (w < SOC_O_BODY_HEIGHT) return E.qvel[va + 6 + (w - SOC_O_JOINTS_VEL)];
+  if (w == SOC_O_BODY_HEIGHT) return E.qpos[qa + 2];
+  if (w >= SOC_O_PREV_ACTION && w < SOC_O_BALL)    // data.ctrl: what the last step applied
+    return a.ctrl_store[(long long)(soc_uadr[p] + (w - SOC_O_PREV_ACTION))*a.nenv + e];
+  real m[9];
+  soccer_mat(&E.qpos[qa + 3], m);
+  if (w < SOC_O_PREV_ACTION) return m[6 + (w - SOC_O_WORLD_ZAXIS)];
+  real v[3] = {0, 0, 0};
+  int dim = 3, j;
+  if (w < SOC_O_OTHERS) {
+    const int k = (w - SOC_O_BALL)/3;
+    j = (w - SOC_O_BALL)%3;
+    if (k == 0) {             // the ball's angular velocity: local -> world first
+      real mb[9];
+      soccer_mat(&E.qpos[SOC_BALL_Q + 3], mb);
+      for (int i = 0; i < 3; i++)
+        v[i] = mb[3*i]*E.qvel[SOC_BALL_V + 3] + mb[3*i + 1]*E.qvel[SOC_BALL_V + 4] +
+               mb[3*i + 2]*E.qvel[SOC_BALL_V + 5];
+    } else if (k == 1) {
+      for (int i = 0; i < 3; i++) v[i] = E.qpos[SOC_BALL_Q + i] - E.qpos[qa + i];
+    } else {
+      for (int i = 0; i < 3; i++) v[i] = E.qvel[SOC_BALL_V + i] - E.qvel[va + i];
+    }
+  } else if (w < SOC_O_ARENA) {
+    const int o = (w - SOC_O_OTHERS)/15, r = (w - SOC_O_OTHERS)%15;
+    const int other = o < p ? o : o + 1;      // every other player in index order
+    const int qo = soc_qadr[other], vo = soc_vadr[other];
+    if (r < 3) {
+      j = r;
+      for (int i = 0; i < 3; i++) v[i] = E.qvel[vo + i] - E.qvel[va + i];
+    } else if (r < 6) {
+      j = r - 3;
+      for (int i = 0; i < 3; i++) v[i] = E.qpos[qo + i] - E.qpos[qa + i];
+    } else {                  // xmat^T . the other's xmat, row-major
+      const int row = (r - 6)/3, col = (r - 6)%3;
+      real mo[9];
+      soccer_mat(&E.qpos[qo + 3], mo);
+      return m[row]*mo[col] + m[3 + row]*mo[3 + col] + m[6 + row]*mo[6 + col];
+    }
+  } else {
+    const int wa = w - SOC_O_ARENA;
+    int s = 0;
+    while (s < 7 && wa >= soc_arena_off[s + 1]) s++;
+    j = wa - soc_arena_off[s];
+    const int f = (s + (p >= SOC_NP/2 ? 4 : 0)) & 7;     // the away team's rotation of the list
+    dim = soc_arena_dim[s];
+    for (int i = 0; i < dim; i++) v[i] = R(soc_feature[3*f + i]) - E.qpos[qa + i];
+  }
+  // v . xmat (2-vectors: the upper-left 2 x 2 block)
+  real out = v[0]*m[j] + v[1]*m[3 + j];
+  if (dim == 3) out += v[2]*m[6 + j];
+  return out;
+}
+// goal code (+1: the ball's centre in the away goal box, -1: in the home one) and
+// off-court flag; compared in double against the fp64 boxes, bounds inclusive, so an
+// fp32 build decides as the host does on the same ball position
+DEV void soccer_game(const Env& E, real& goal, real& off) {
+  bool home = true, away = true, in = true;
+  for (int i = 0; i < 3; i++) {
+    const double c = (double)E.qpos[SOC_BALL_Q + i];
+    home = home && c >= soc_home_lo[i] && c <= soc_home_hi[i];
+    away = away && c >= soc_away_lo[i] && c <= soc_away_hi[i];
+    if (i < 2) in = in && c >= soc_field_lo[i] && c <= soc_field_hi[i];
+  }
+  goal = away ? R(1) : (home ? R(-1) : R(0));
+  off = in ? R(0) : R(1);
+}
+DEV void soccer_outputs(const Env& E, const DmcArgs& a, int e, bool accumulate) {
+  const long long n = a.nenv;
+  tsync();
+  real goal, off;
+  soccer_game(E, goal, off);
+  for (int k = tlane(); k < NOBS; k += TEAM) {
+    real x;
+    if (k < SOC_NP*SOC_D) x = soccer_word(E, a, e, k/SOC_D, k%SOC_D);
+    else x = k == SOC_NP*SOC_D ? goal : off;
+    a.obs[(long long)k*a.obs_sk + (long long)e*a.obs_se] = x;
+  }
+  if (tlane() == 0) {
+    a.reward[e] = goal;                 // the home team's reward
+    if (accumulate) a.episode_return[e] += goal;
+    if (a.xpos) for (int i = 0; i < NBODY*3; i++) a.xpos[i*n + e] = E.xpos[i];
+    if (a.xmat) for (int i = 0; i < NBODY*9; i++) a.xmat[i*n + e] = E.xmat[i];
+    a.stats[e] = E.ncon; a.stats[n + e] = E.nefc + E.nmerged; a.stats[2*n + e] = E.iters;
+  }
+}
+#endif  // DMC_TASK_SOCCER
+
 DEV void store_outputs(Env& E, const DmcArgs& a, int e, bool accumulate,
                        real* lds_base, unsigned long long live = ALL_LANES) {
   const long long n = a.nenv;
+#ifdef DMC_TASK_SOCCER
+  soccer_outputs(E, a, e, accumulate);
+  return;
+#endif
   if (TEAMED && TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0) {
     // no task: the observation is the (shared) state, every lane copies its share
     tsync();
@@ -5260,11 +5381,13 @@ dmc_step(DmcArgs a) {
   team_bind(E, W);
   load_env(E, a, e, time);
   const real tol = R(tolerance_opt > DMC_TOL_FLOOR ? tolerance_opt : DMC_TOL_FLOOR);
-  const int nsteps = (TEAMED || a.nsteps < 1) ? 1 : a.nsteps;
+  const int nsteps = (TEAMED || TASK == TASK_SOCCER || a.nsteps < 1) ? 1 : a.nsteps;
   const bool outputs = !(a.flags & DMC_FLAG_NO_OUTPUT);
   // the observation stage computes the frames (a model without a task: the
   // observation is qpos and qvel; the frames are only recomputed if someone reads them)
-  const bool frames = !(TASK == TASK_NONE && NSENSOR == 0 && NTOUCH == 0 && !a.xpos && !a.xmat);
+  // (TASK_SOCCER reads the players' frames off their root quaternions)
+  const bool frames = !((TASK == TASK_NONE || TASK == TASK_SOCCER) && NSENSOR == 0 && NTOUCH == 0 &&
+                        !a.xpos && !a.xmat);
   real ret = 0;               // register copy of the episode return
   if (!TEAMED && outputs) ret = a.episode_return[e];
 #ifdef DMC_ROLLOUT
@@ -5375,7 +5498,9 @@ dmc_step(DmcArgs a) {
     a.episode_return[e] = ret;
   }
 #else
-  if (!TEAMED && outputs) {      // the last step's outputs
+  if (!TEAMED && outputs && TASK == TASK_SOCCER) {     // (one step per launch, as in team mode)
+    store_outputs(E, a, e, true, lds_rows, live);
+  } else if (!TEAMED && outputs) {      // the last step's outputs
     real obs[NOBS > 0 ? NOBS : 1];
     const real rew = task_outputs(E, a, obs);
     ret += rew;
@@ -5571,7 +5696,7 @@ extern "C" __device__ const DmcInfo dmc_info = {
     .npair = NPAIR,
     .envs_per_block = LANES/TEAM,   // (= its threads unless a team of lanes shares an env)
     .env_major = DMC_ENV_MAJOR, .ntaskdata = NTASKDATA, .threads_per_block = LANES,
-    .nmodelparam = DMC_NMODELPARAM, .seq_launch = TEAMED ? 0 : 1};
+    .nmodelparam = DMC_NMODELPARAM, .seq_launch = (TEAMED || TASK == TASK_SOCCER) ? 0 : 1};
 extern "C" __device__ const DmcEpisodeCaps dmc_episode_caps = EPISODE_CAPS;
 #ifdef DMC_ROLLOUT
 extern "C" __device__ const DmcRolloutCaps dmc_rollout_caps = ROLLOUT_CAPS;

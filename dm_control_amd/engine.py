@@ -694,6 +694,12 @@ class Physics(_control.Physics):
       self.forward()
 
   # -- fused task outputs ---------------------------------------------------------
+  @property
+  def outputs_stale(self):
+    """True: the state changed (set_state, a field write, a step without outputs)
+    since the observation and reward fields were written."""
+    return self._dirty
+
   def _ensure_outputs(self):
     if self._dirty:
       self.forward()

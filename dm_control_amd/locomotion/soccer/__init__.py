@@ -13,9 +13,10 @@ What is built, and what it replaces:
              47, condim 6, priority 1), 2 x team_size position-controlled CMU
              humanoids (walkers/cmu_humanoid.py), `disable_walker_contacts`
              (task.py:29-33).  One frozen MJCF per (team_size, pitch size).
-  physics    the whole scene is one model (2v2: nv 254) stepped by the
-             one-env-per-lane kernel in its rolled form with the packed
-             matrices in the HBM workspace (csrc/dmc_kernels.hip, MAT_IN_WS).
+  physics    the whole scene is one model (2v2: nv 254) stepped by the team
+             build of csrc/dmc_kernels.hip: one wavefront per pitch, the packed
+             matrices, constraint rows and contacts in the HBM workspace
+             (MAT_IN_WS), one kinematic tree's block at a time in LDS.
   game logic `Task`: goal detection (the ball's centre inside a goal box:
              pitch.py:426-447, 574-580), reward +1 / -1 per player and discount
              0 on a goal (task.py:161-200), throw-in when the ball leaves the
@@ -28,6 +29,13 @@ What is built, and what it replaces:
              other player (position, linear velocity, orientation) and the eight
              arena features, all in the player's egocentric frame
              (composer/entity.py:340-375: v . xmat).
+  on device  `load(..., fused_task=True)`: the observables, the goal code and
+             the off-court flag are an output stage of the step kernel
+             (TASK_SOCCER, csrc/dmc_kernels.hip `soccer_outputs`; the row is
+             `codegen.soccer_observation_layout`).  `FusedTask` slices one read
+             of the observation field; `SoccerVecEnv` hands the field out as a
+             torch view and reads two words per pitch and step.  Kick-off and
+             throw-in stay the host recipes below, draw for draw.
 
 Stated deviations: the pitch size is fixed per environment (`RandomizedPitch`
 redraws it every episode and the reference recompiles the model,
@@ -44,7 +52,10 @@ import enum
 import numpy as np
 
 from dm_control_amd import _dm_env as dm_env
+from dm_control_amd import codegen
 from dm_control_amd import engine
+from dm_control_amd import wrapper
+from dm_control_amd.mjcf import compiler
 from dm_control_amd.locomotion.models import soccer as scene
 from dm_control_amd.rl import control
 from dm_control_amd.suite import common
@@ -332,6 +343,90 @@ class Task(control.Task):
     return out
 
 
+class FusedTask(Task):
+  """`Task` over a `Physics` built with TASK_SOCCER: observables, goals and
+  balls off court come from the observation field the step kernel wrote (one
+  [B, NOBS] read per control step); the state is read back only for the host
+  recipes, kick-off and throw-in, when some pitch needs one."""
+
+  def __init__(self, *args, **kwargs):
+    super().__init__(*args, **kwargs)
+    self.layout = codegen.soccer_observation_layout(
+        self.num_players, (NQ_WALKER, NV_WALKER, NU_WALKER))
+    self._game_at = self.layout['game'][0]
+    self._row = None        # the observation field as last read, [B, NOBS]
+    self._off = None        # [B] bool: the device's off-court flag of the current state
+
+  def set_game(self, game):
+    """Takes the game block [B, 2] of the current state (goal code, off court)."""
+    game = np.asarray(game)
+    scored = np.full(len(game), -1)
+    scored[game[:, 0] < 0] = 1        # away team scores
+    scored[game[:, 0] > 0] = 0
+    self._off = game[:, 1] != 0
+    return scored
+
+  def _read(self, physics):
+    if self._row is None or physics.outputs_stale:
+      self._row = np.atleast_2d(physics.fused_observation())
+      self._off = self._row[:, self._game_at + 1] != 0
+    return self._row
+
+  def initialize_episode(self, physics, only=None):
+    super().initialize_episode(physics, only=only)
+    self._row = self._off = None
+
+  def _throw_in(self, physics, mask):
+    super()._throw_in(physics, mask)
+    self._row = self._off = None
+
+  def restarts(self, physics):
+    """Kick-off where a goal ended the last rally, throw-in for balls off court."""
+    if physics.outputs_stale:     # somebody moved the state since the flags were written
+      self._row = self._off = None
+    kicked = self._scored is not None and (self._scored >= 0).any()
+    if kicked:
+      self.initialize_episode(physics, only=self._scored >= 0)
+      self._scored[:] = -1
+    if self._off is None:       # after a kick-off (or before any read): the host's test
+      ball = np.atleast_2d(np.asarray(physics.data.qpos, np.float64))[
+          :, self._ball_q:self._ball_q + 3]
+      out = self.pitch.off_court(ball)
+    else:
+      out = self._off
+    if out.any():
+      self._throw_in(physics, out)
+
+  def before_step(self, action, physics):
+    n = physics.batch_size or 1
+    if isinstance(action, (list, tuple)):
+      action = np.concatenate([np.atleast_2d(a) for a in action], axis=-1)
+    action = np.asarray(action, np.float64).reshape(n, physics.model.nu)
+    self._prev_action = action
+    self.restarts(physics)
+    physics.set_control(action if physics.batch_size else action[0])
+    self._row = self._off = None
+
+  def after_step(self, physics):
+    row = self._read(physics)
+    self._scored = self.set_game(row[:, self._game_at:self._game_at + 2])
+
+  def get_observation(self, physics):
+    row = self._read(physics)
+    out = []
+    for k in range(self.num_players):
+      obs = control.BatchedObservation()
+      obs.batch_size = physics.batch_size
+      for (player, name), (offset, extent) in ((key, v) for key, v in self.layout.items()
+                                               if key != 'game'):
+        if player != k:
+          continue
+        leaf = row[:, offset] if name == 'body_height' else row[:, offset:offset + extent]
+        obs[name] = leaf.copy() if physics.batch_size else leaf[0].copy()
+      out.append(obs)
+    return out
+
+
 def _quat_mul(a, b):
   aw, ax, ay, az = a
   bw, bx, by, bz = b
@@ -352,13 +447,16 @@ class Environment(control.Environment):
 def load(team_size, time_limit=45., random_state=None, disable_walker_contacts=False,
          enable_field_box=False, keep_aspect_ratio=False, terminate_on_goal=True,
          walker_type=WalkerType.HUMANOID, pitch_size=None, control_timestep=0.025,
-         environment_kwargs=None):
+         environment_kwargs=None, fused_task=False):
   """`team_size`-vs-`team_size` soccer (signature of soccer/__init__.py:92-99, the
   walker type defaulting to the one that is built).
 
   pitch_size: (half length, half width); default: the smallest mini-football
   pitch for this many humanoids (soccer/__init__.py:130-135).
   environment_kwargs: `batch_size`, `device`, `precision` for the batched Physics.
+  fused_task: True builds the physics with the soccer task layer as an output
+  stage of the step kernel (`FusedTask`): same seed and actions give the same
+  TimeStep stream up to the rounding of the observables.
   """
   del keep_aspect_ratio      # the pitch does not change between episodes
   if not 1 <= team_size <= 11:
@@ -381,8 +479,105 @@ def load(team_size, time_limit=45., random_state=None, disable_walker_contacts=F
   # (tools/debug/soccer_soak.py; 16 per player raised mjWARN_CONTACTFULL in 71 of
   # them); beyond the capacity the step raises mjWARN_CONTACTFULL like the reference
   phys_kw.setdefault('ncon_max', 40*num_walkers)
-  physics = Physics.from_xml_string(xml, **phys_kw)
-  task = Task(team_size, geometry, random=random_state,
-              terminate_on_goal=terminate_on_goal)
+  if fused_task:
+    model = compiler.from_xml_string(xml)
+    # (compiled into the kernel, part of the code object's key: codegen.soccer_pitch_of)
+    model.soccer_pitch = geometry.size + geometry.goal_size
+    physics = Physics(model, task=codegen.TASK_SOCCER, **phys_kw)
+  else:
+    physics = Physics.from_xml_string(xml, **phys_kw)
+  task = (FusedTask if fused_task else Task)(team_size, geometry, random=random_state,
+                                             terminate_on_goal=terminate_on_goal)
   return Environment(physics, task, time_limit=time_limit,
                      control_timestep=control_timestep, **env_kw)
+
+
+class SoccerVecEnv:
+  """Torch adaptor over the fused soccer environment: B pitches, observations
+  and rewards stay on the device.
+
+  `reset()` -> obs [B, P, D]; `step(actions [B, P, nu])` -> (obs, rewards [B, P],
+  dones [B], infos).  `obs` is a VIEW of the observation field the step kernel
+  writes (`layout`: name -> slice of D): it changes with the next step, clone
+  what has to last.  Per control step the host reads the game block (2 words per
+  pitch) to see whether a pitch needs a kick-off or a throw-in -- the host
+  recipes of `Task`, draw for draw; nothing else on the step path reads from the
+  device (bad states are not checked: `environment.physics.check_invalid_state()`).
+  The B pitches share the time limit: `dones` is true for all at once, and the
+  step that reaches it resets (`infos['terminal_observation']`).
+  """
+
+  def __init__(self, team_size, num_envs, seed=None, torch_io=True, **load_kwargs):
+    if not torch_io:
+      raise ValueError('SoccerVecEnv is the torch adaptor; the numpy path is '
+                       'soccer.load(..., fused_task=True)')
+    import torch
+    from dm_control_amd import torch_io as tio
+    env_kw = dict(load_kwargs.pop('environment_kwargs', None) or {})
+    env_kw['batch_size'] = int(num_envs)
+    load_kwargs.setdefault('random_state', seed)
+    load_kwargs['fused_task'] = True
+    self._env = load(team_size, environment_kwargs=env_kw, **load_kwargs)
+    self._physics, self._task = self._env.physics, self._env.task
+    self._batch = self._physics.batch
+    self.num_envs, self.num_players = int(num_envs), 2*int(team_size)
+    self.action_dim = NU_WALKER
+    self._nsub = self._env._n_sub_steps          # pylint: disable=protected-access
+    self._step_limit = self._env._step_limit     # pylint: disable=protected-access
+    self._count = 0
+    tio.use_current_stream(self._batch)
+    self._obs_t = tio.field_tensor(self._batch, wrapper.FIELD_OBS)      # [B, NOBS]
+    at = self._task.layout['game'][0]
+    self.observation_dim = at//self.num_players
+    self._players = self._obs_t[:, :at].unflatten(1, (self.num_players, self.observation_dim))
+    self._game = self._obs_t[:, at:at + 2]
+    half = self.num_players//2
+    self._sign = torch.tensor([1.0]*half + [-1.0]*half, dtype=self._obs_t.dtype,
+                              device=self._obs_t.device)
+    self.layout = collections.OrderedDict(
+        (name, slice(offset, offset + extent))
+        for (player, name), (offset, extent) in (
+            (key, v) for key, v in self._task.layout.items() if key != 'game')
+        if player == 0)
+
+  @property
+  def environment(self):
+    return self._env
+
+  def reset(self):
+    with self._physics.reset_context():
+      self._task.initialize_episode(self._physics)
+    self._count = 0
+    self._task.set_game(self._game.cpu().numpy())      # (off court at kick-off: a tiny pitch)
+    return self._players
+
+  def step(self, actions):
+    import torch
+    if not actions.is_cuda:
+      raise ValueError('SoccerVecEnv expects CUDA action tensors')
+    shape = (self.num_envs, self.num_players, self.action_dim)
+    if tuple(actions.shape) != shape:
+      raise ValueError('actions must have shape %r, got %r' % (shape, tuple(actions.shape)))
+    a = actions.to(self._obs_t.dtype).reshape(self.num_envs, -1).contiguous()
+    self._keepalive = a
+    task, physics = self._task, self._physics
+    task.restarts(physics)          # (reads the state back only where a pitch is flagged)
+    physics.set_control_device(a.data_ptr(), 1, a.stride(0))
+    physics.step(self._nsub, check=False)
+    self._count += 1
+    goal = self._game[:, 0].clone()
+    task._scored = task.set_game(self._game.cpu().numpy())   # pylint: disable=protected-access
+    rewards = goal[:, None]*self._sign[None, :]
+    discount = torch.ones_like(goal)
+    if task._terminate_on_goal:                  # pylint: disable=protected-access
+      discount = torch.where(goal != 0, torch.zeros_like(goal), discount)
+    done = self._count >= self._step_limit
+    dones = torch.full((self.num_envs,), bool(done), device=goal.device)
+    infos = {'goal': goal, 'discount': discount}
+    if done:
+      infos['terminal_observation'] = self._players.clone()
+      self.reset()
+    return self._players, rewards, dones, infos
+
+  def close(self):
+    self._physics.free()
